@@ -1,6 +1,6 @@
 """bench.py — registered Frame360 pairs/sec on MI355X (BASELINE.json metric) + ICP-reduce roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sequence|dense]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sequence|dense] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,6 +21,15 @@ One step registers each of the 255 consecutive pairs exactly once (rgbd360_amd/o
     region.
 Strong scaling: the sequence is the same at every N.  Workload "dense" (configs[2]; configs[4] with
 --rows 960 --cols 1280 --iters0 50): stitch + pyramid of every frame and alignFrames360 per pair, no planes.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the figures the timed steps
+themselves yield: the level-0 pass's in-kernel roofline, the host split, the queues' batches).  --dump-outputs DIR also
+writes what the last timed step returned to its caller, as DIR/records.npy (the pair records of the whole sequence,
+float32) and DIR/trajectory.npy (the composed trajectory, float64): the inputs are the same seeded sequence in every
+run, so two builds can be compared array for array.  --full adds everything that takes runs or checks of its own: the
+records check against the warm-up step, the trajectory error against the synthetic ground truth, the HBM-resident
+rerun, the lone pair, the CPU baseline, the sequential caller, config 1, the two halves (configs 2 and 3) and the
+config-5 HiRes leg (each of them can still be left out with its --no-... switch).
 
 Prints ONE JSON line on rank 0.
 """
@@ -502,6 +511,13 @@ def main(argv=None, runner_factory=None):
                          "planes on its own stream)")
     ap.add_argument("--emulate", type=str, default=None,
                     help="RANK/WORLD: run that rank's shard alone (single-GPU rehearsal of an N-GPU shard)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/records.npy (pair records, float32) and "
+                         "DIR/trajectory.npy (composed trajectory, float64); rank 0 writes them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs and checks (records check, trajectory error, "
+                         "HBM-resident rerun, lone pair, CPU baseline, sequential caller, configs 1, 2, 3 and 5); the "
+                         "--no-... switches below leave single legs out of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-resident", action="store_true", help="skip the HBM-resident-input secondary run")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 (8x1280x960, 50 iterations) leg")
@@ -511,6 +527,8 @@ def main(argv=None, runner_factory=None):
                          "the warmup and timed launches)")
     ap.add_argument("--eval-probe", action="store_true", help="diagnostic: also time the level-0 pass in eval mode")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -673,13 +691,15 @@ def main(argv=None, runner_factory=None):
     value = pairs_job / elapsed
     # every timed step's pair records against the first warm-up step's, bit for bit (the same pairs, registered in
     # other pipeline pieces and dense batches): a wrong frame buffer at a piece's repeat boundary would show here
-    records_same = {"timed_steps": bool((rec == wrec[0][None]).all()),
-                    "warmup_steps": bool((wrec == wrec[0][None]).all())}
+    records_same = {}
+    if args.full:
+        records_same = {"timed_steps": bool((rec == wrec[0][None]).all()),
+                        "warmup_steps": bool((wrec == wrec[0][None]).all())}
 
     # secondary: the same steps with the raw images already resident in HBM (device-to-device copies
     # into the frames instead of PCIe uploads)
     resident = None
-    if not args.no_resident:
+    if args.full and not args.no_resident:
         dB, dD = R.DeviceArray(local, BGR), R.DeviceArray(local, DEP)
 
         def dev_of(i):
@@ -717,7 +737,7 @@ def main(argv=None, runner_factory=None):
     # a lone pair on an idle GPU (OdometryRGBD360's sequential caller registers one pair at a time): the sequence's
     # first two frames built through the façade, alignFrames360 with the same schedule, nothing else running
     iso_ms, n, iso_ach, lone_ms, lone_mean_ms = 0.0, 0, None, None, None
-    if not args.no_isolated:
+    if args.full and not args.no_isolated:
         # two consecutive frames of the sequence, built as a caller of the façade builds them, on a context of their
         # own (the runner's queued ring frames skip the compacted level-0 points a lone pass reads)
         ictx = R.Context(local)
@@ -845,27 +865,35 @@ def main(argv=None, runner_factory=None):
         **({"per_rank": per_rank} if per_rank else {"gather_ms": gather_s * 1e3}),
         "frame_generation_s": round(gen_s, 1),
     }
-    if rank == 0 and traj is not None:
+    if not args.full:   # the plain line holds only what the timed steps themselves yield
+        for k in ("value_hbm_resident_inputs", "records_identical", "records_check"):
+            del out[k]
+        del out["roofline"]["isolated"]
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "records.npy"), np.ascontiguousarray(allrec[-1], np.float32))
+        np.save(os.path.join(args.dump_outputs, "trajectory.npy"), np.ascontiguousarray(traj, np.float64))
+    if args.full and rank == 0 and traj is not None:
         gt = np.stack([R.synth_path_pose(SEED, k).astype(np.float64) for k in range(args.frames)])
         if allrec.shape[1] == args.frames - 1:
             out["trajectory"] = OD.trajectory_error(traj, gt)
             st = allrec[-1, :, OD.R_STATUS]
             out["trajectory"].update({"pairs": int(allrec.shape[1]), "pbmap_failed": int((st == 1).sum()),
                                       "illposed": int((st == 2).sum())})
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(runner.cals[0], frames_of, p0, p1, args.workload, args.iters0)
     runner.close()
-    if rank == 0 and world == 1 and not args.no_halves and args.workload == "sequence":
+    if args.full and rank == 0 and world == 1 and not args.no_halves and args.workload == "sequence":
         out["sequential_cpp"] = sequential_leg(local, args.rows, args.cols, p0, frames_of, params)
         out["config1"] = config1_leg(local)
     # configs[1] and configs[2] (the two halves of each pair's work) over the same sequence, after the timed region
-    if rank == 0 and world == 1 and not args.no_halves and args.workload == "sequence":
+    if args.full and rank == 0 and world == 1 and not args.no_halves and args.workload == "sequence":
         out["config2"] = half_leg("planes", local, args.rows, args.cols, p0, p1, frames_of, params, args.streams,
                                   args.queue, args.depth)
         out["config3"] = half_leg("dense", local, args.rows, args.cols, p0, p1, frames_of, params, args.streams,
                                   args.queue, args.depth)
     pinned.close()
-    if rank == 0 and world == 1 and not args.no_config5 and args.workload == "sequence" and args.rows == 480:
+    if args.full and rank == 0 and world == 1 and not args.no_config5 and args.workload == "sequence" and args.rows == 480:
         del BGR, DEP
         out["config5"] = config5_leg(local, rt8)
     if rank == 0:

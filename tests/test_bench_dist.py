@@ -171,7 +171,7 @@ def _main_worker(rank, world, port, out_dir):
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--frames", "24", "--rows", "24",
-                    "--cols", "32", "--streams", "3", "--min-run", "2", "--no-cpu-baseline", "--no-resident",
+                    "--cols", "32", "--streams", "3", "--min-run", "2", "--full", "--no-cpu-baseline", "--no-resident",
                     "--no-config5", "--no-isolated"], runner_factory=_StubRunner)
     with open(os.path.join(out_dir, f"out{rank}.txt"), "w") as f:
         f.write(buf.getvalue())
@@ -209,3 +209,49 @@ def test_bench_main_multi_rank(tmp_path, world):
     assert [r["rank"] for r in pr] == list(range(world)) and [r["pairs_per_step"] for r in pr] == sizes
     assert all(r["pairs_per_s"] > 0 and r["gather_ms"] >= 0 and r["halo_frames_per_step"] >= 1 for r in pr)
     assert max(r["timed_s"] for r in pr) == pytest.approx(out["ms_per_step"] * 2e-3, rel=1e-5)
+
+
+class _CountingRunner(_StubRunner):
+    """The stand-in, recording how many repeats each run() call was asked for."""
+    calls = []
+
+    def run(self, p0, p1, frames_of, out, repeats=1, runs=None, device_inputs=False):
+        _CountingRunner.calls.append(repeats)
+        super().run(p0, p1, frames_of, out, repeats=repeats, runs=runs, device_inputs=device_inputs)
+
+
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path, monkeypatch, capsys):
+    """A run without --full does the warm-up and the timed steps and nothing after them: exactly two runner calls
+    (--warmup, then --steps repeats), a line with the headline fields and none of the secondary legs or checks.
+    --dump-outputs writes the last timed step's records (float32) and the trajectory composed from them (float64),
+    the same arrays from run to run."""
+    import json
+    for k, v in dict(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", R360_NO_PIN="1").items():
+        monkeypatch.setenv(k, v)
+    dumps = []
+    for d in ("a", "b"):
+        _CountingRunner.calls = []
+        bench.main(["--gpus", "1", "--steps", "3", "--warmup", "2", "--frames", "24", "--rows", "24", "--cols", "32",
+                    "--streams", "3", "--dump-outputs", str(tmp_path / d)], runner_factory=_CountingRunner)
+        assert _CountingRunner.calls == [2, 3]
+        lines = capsys.readouterr().out.strip().splitlines()
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["metric"] == bench.METRIC and out["unit"] == "pairs/s" and out["dtype"] == "f32"
+        assert out["higher_is_better"] is True and out["steps"] == 3 and out["warmup"] == 2
+        assert out["value"] > 0 and abs(out["value"] - 3 * 23 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+        for k in ("cpu_baseline", "sequential_cpp", "config1", "config2", "config3", "config5", "trajectory",
+                  "value_hbm_resident_inputs", "records_identical", "records_check"):
+            assert k not in out, k
+        assert "isolated" not in out["roofline"]
+        assert sorted(os.listdir(tmp_path / d)) == ["records.npy", "trajectory.npy"]
+        dumps.append((np.load(tmp_path / d / "records.npy"), np.load(tmp_path / d / "trajectory.npy")))
+    rec, traj = dumps[0]
+    assert rec.dtype == np.float32 and rec.shape == (23, OD.REC)
+    assert traj.dtype == np.float64 and traj.shape == (24, 4, 4)
+    assert np.array_equal(traj, OD.compose(rec))
+    import rgbd360_amd as R
+    rel = np.linalg.inv(R.synth_path_pose(bench.SEED, 5).astype(np.float64)) @ \
+        R.synth_path_pose(bench.SEED, 6).astype(np.float64)
+    assert np.array_equal(rec[5, :16], rel.T.reshape(16).astype(np.float32))   # the stand-in's record of pair 5
+    assert np.array_equal(rec, dumps[1][0]) and np.array_equal(traj, dumps[1][1])

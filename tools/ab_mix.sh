@@ -5,7 +5,7 @@ set -o pipefail
 TAG=$1; REPS=$2; shift 2
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/abm_$TAG; mkdir -p $O
 one() { local name=$1 dir=$2 envs=$3 a=$4
-  (cd $R/$dir && env $envs timeout -k 10 200 python3 -u bench.py --no-cpu-baseline --no-resident --no-config5 ${ISO:+--no-isolated} --no-halves --steps 10 --warmup 2 $a > $O/$name.json 2> $O/$name.err) || { echo "$name failed"; tail -5 $O/$name.err; exit 4; }
+  (cd $R/$dir && env $envs timeout -k 10 200 python3 -u bench.py --full --no-cpu-baseline --no-resident --no-config5 ${ISO:+--no-isolated} --no-halves --steps 10 --warmup 2 $a > $O/$name.json 2> $O/$name.err) || { echo "$name failed"; tail -5 $O/$name.err; exit 4; }
   python3 -c "
 import json; d=json.load(open('$O/$name.json')); r=d['roofline']; h=d['pipeline_host_ms_per_pair']
 ppl = r.get('pairs_per_launch') or 0; l0 = r['avg_launch_ms']*1e3/ppl if ppl else 0.0

@@ -9,7 +9,7 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout
 tail -2 $O/gpu_tests.log
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 2; }
 tail -3 $O/smoke.log
-timeout -k 10 500 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
+timeout -k 10 500 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); r=d['roofline']; c=d.get('config5',{}); cr=c.get('roofline',{})
 print('bench', round(d['value'],1), 'pairs/s, resident', round(d['value_hbm_resident_inputs'] or 0,1), 'frac', round(r['frac'],3), 'traffic', r['traffic'],

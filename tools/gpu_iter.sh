@@ -12,7 +12,7 @@ fi
 timeout -k 10 180 python -u tools/icp_bench.py 30 > $O/icp_bench.txt 2>&1 || { echo "icp_bench failed"; tail $O/icp_bench.txt; exit 2; }
 POSE=path timeout -k 10 180 python -u tools/icp_bench.py 30 >> $O/icp_bench.txt 2>&1 || { echo "icp_bench path failed"; exit 3; }
 cat $O/icp_bench.txt
-timeout -k 10 300 python -u bench.py --no-cpu-baseline ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 4; }
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline ${BENCH_ARGS} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail $O/bench.err; exit 4; }
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); r=d['roofline']
 print('value', round(d['value'],1), 'resident', round(d['value_hbm_resident_inputs'] or 0,1), 'L0 pipeline us', round(r['avg_launch_ms']*1e3,1), 'frac', round(r['frac'],3), 'isolated us', round(r['isolated']['avg_launch_ms']*1e3,1), 'frac', round(r['isolated']['frac'],3))"

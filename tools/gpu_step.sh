@@ -20,7 +20,7 @@ for st in "$@"; do
       timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 2; }
       tail -2 $O/smoke.log ;;
     bench)
-      timeout -k 10 500 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
+      timeout -k 10 500 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 3; }
       python3 tools/bench_line.py $O/bench.json ;;
     quick)
       timeout -k 10 200 python -u bench.py $Q > $O/quick.json 2> $O/quick.err || { tail -20 $O/quick.err; exit 4; }

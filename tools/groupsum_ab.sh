@@ -16,6 +16,6 @@ tail -1 $O/gpu_tests.log
 i=0
 for v in "" _flat "" _flat; do
   i=$((i+1))
-  R360_LIB=$L/librgbd360_hip$v.so timeout -k 10 200 python -u bench.py --no-cpu-baseline --no-resident --no-config5 --steps 5 --warmup 1 > $O/bench${v}_$i.json 2> $O/bench${v}_$i.err || { tail $O/bench${v}_$i.err; exit 4; }
+  R360_LIB=$L/librgbd360_hip$v.so timeout -k 10 200 python -u bench.py --full --no-cpu-baseline --no-resident --no-config5 --steps 5 --warmup 1 > $O/bench${v}_$i.json 2> $O/bench${v}_$i.err || { tail $O/bench${v}_$i.err; exit 4; }
   python3 -c "import json; d=json.load(open('$O/bench${v}_$i.json')); r=d['roofline']; print('lib$v', round(d['value'],1), 'pairs/s  L0', round(r['avg_launch_ms']*1e3,2), 'us frac', round(r['frac'],3), ' lone L0', round(r['isolated']['avg_launch_ms']*1e3,2), 'us align', round(r['isolated']['align_ms_per_pair'],3), 'ms')"
 done

@@ -9,11 +9,11 @@
 # copies back at most 64 MiB.
 set -o pipefail
 TAG=${1:-r1}; shift
-R=$GRAFT_REPO_ROOT
-OUT=$R/gpurun_out/prof_$TAG
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT_ROOT:-$R/build/bench_out}/prof_$TAG   # OUT_ROOT: where the profiles go
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 1 --no-cpu-baseline --no-resident $*"
+ARGS="--full --steps 1 --warmup 1 --no-cpu-baseline --no-resident $*"   # --full: the lone pair, the halves and config 5 are profiled too
 TARGS="--streams 4 $ARGS"
 rc=0
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $R/bench.py $TARGS > $OUT/trace_bench.json 2> $OUT/trace.err || rc=1
