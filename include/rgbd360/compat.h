@@ -28,6 +28,7 @@
 #include <string>
 
 using r360::Calib360;
+using r360::FilterPointCloud;
 using r360::Frame360;
 using r360::PbMap;
 using r360::Plane;

@@ -152,6 +152,32 @@ struct Mat {
     bool empty() const { return rows == 0 || cols == 0; }
 };
 
+// Host point cloud (pcl::PointCloud<pcl::PointXYZRGBA> stand-in): xyz triples and PointXYZRGBA-packed colours
+// (b | g<<8 | r<<16 | a<<24); organised when height > 1.
+struct PointCloud {
+    std::vector<float> xyz;             // [size][3]
+    std::vector<uint32_t> rgba;         // [size]
+    int width = 0, height = 0;
+    size_t size() const { return rgba.size(); }
+    bool empty() const { return rgba.empty(); }
+    // n points, unorganised (what a filter leaves)
+    void resize(size_t n) {
+        xyz.resize(3 * n);
+        rgba.resize(n);
+        width = int(n);
+        height = 1;
+    }
+    void clear() { resize(0); }
+    // concatenation: the result is unorganised, as pcl::PointCloud::operator+= leaves it
+    PointCloud& operator+=(const PointCloud& o) {
+        xyz.insert(xyz.end(), o.xyz.begin(), o.xyz.end());
+        rgba.insert(rgba.end(), o.rgba.begin(), o.rgba.end());
+        width = int(rgba.size());
+        height = 1;
+        return *this;
+    }
+};
+
 class Context {
   public:
     explicit Context(int device = 0) { check(r360_ctx_create(device, &h_), "r360_ctx_create"); }
@@ -323,6 +349,7 @@ class Frame360 {
         rgba.resize(n);
         check(r360_frame_get_sphere_cloud(h_, xyz.data(), rgba.data(), n, &width, &height), "sphereCloud");
     }
+    void sphereCloud(PointCloud& cloud) { sphereCloud(cloud.xyz, cloud.rgba, cloud.width, cloud.height); }
     // Frame360::getPlanarArea (Frame360.h:157)
     float getPlanarArea() const {
         float a = 0.f;
@@ -675,6 +702,52 @@ class BatchRegistration {
     r360_batch* get() const { return h_; }
   private:
     r360_batch* h_ = nullptr;
+};
+
+// ------------------------------------------------------------------ point-cloud filters (FilterPointCloud.h)
+// pcl::transformPointCloud(in, out, T): m(k,0)*x + m(k,1)*y + m(k,2)*z + m(k,3) per component in float, left to
+// right and never contracted into FMAs; a point with a non-finite coordinate stays as it is (non-dense clouds).
+#if defined(__clang__)
+#define R360_NO_FP_CONTRACT
+#elif defined(__GNUC__)
+#define R360_NO_FP_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define R360_NO_FP_CONTRACT
+#endif
+R360_NO_FP_CONTRACT inline void transformPointCloud(const PointCloud& in, PointCloud& out, const Matrix4f& T) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    if (&in != &out) { out.rgba = in.rgba; out.width = in.width; out.height = in.height; out.xyz.resize(in.xyz.size()); }
+    const float* m = T.data();   // column-major
+    for (size_t i = 0; i < in.size(); ++i) {
+        const float x = in.xyz[3 * i], y = in.xyz[3 * i + 1], z = in.xyz[3 * i + 2];
+        float* o = &out.xyz[3 * i];
+        if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z)) { o[0] = x; o[1] = y; o[2] = z; continue; }
+        for (int k = 0; k < 3; ++k) {
+            float a = m[k] * x;
+            a = a + m[4 + k] * y;
+            a = a + m[8 + k] * z;
+            o[k] = a + m[12 + k];
+        }
+    }
+}
+
+// FilterPointCloud (include/FilterPointCloud.h) with the reference's constructor defaults: filterEuclidean works
+// on the cloud in place, on the host, and leaves it unorganised.  (filterVoxel is not provided.)
+class FilterPointCloud {
+  public:
+    FilterPointCloud(const float voxelSize = 0.05f, const float euclideanBox = 4.0f)
+        : box_(euclideanBox) { (void)voxelSize; }
+    void filterEuclidean(PointCloud& cloud) {
+        size_t n = 0;
+        check(r360_cloud_filter_euclidean(cloud.xyz.data(), cloud.rgba.data(), cloud.size(), -2.0f, 1.0f, box_,
+                                          cloud.xyz.data(), cloud.rgba.data(), &n),
+              "filterEuclidean");
+        cloud.resize(n);
+    }
+  private:
+    float box_;
 };
 
 }  // namespace r360

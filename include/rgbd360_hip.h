@@ -628,6 +628,15 @@ int r360_ctx_kernel_stats(r360_ctx* ctx, int level, double* us_sum, long* launch
 int r360_ctx_host_times(r360_ctx* ctx, double out[6], int reset);
 int r360_ctx_kernel_time_reset(r360_ctx* ctx);
 
+/* ---------------------------------------------------------------- FilterPointCloud
+ * FilterPointCloud::filterEuclidean (include/FilterPointCloud.h; SLAM/SphereGraphSLAM.cpp:116, :193) on the host
+ * (no GPU), restated from PCL 1.7's PassThrough: keeps a point iff x, y, z are finite and x_min <= x <= x_max,
+ * -box <= y <= box, -box <= z <= box (float compares, closed intervals; the reference uses -2, 1 and 4).  Order is
+ * kept and the result is unorganised.  xyz [n][3], rgba [n] PointXYZRGBA packing (NULL: none); the outputs may be
+ * the inputs. */
+int r360_cloud_filter_euclidean(const float* xyz, const uint32_t* rgba, size_t n, float x_min, float x_max, float box,
+                                float* out_xyz, uint32_t* out_rgba, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

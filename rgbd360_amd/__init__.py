@@ -289,6 +289,8 @@ _SIGS = [
     ("r360_ctx_latency_mode", C.c_int, [_P, C.c_int]),
     ("r360_ctx_timing_read", C.c_int, [_P, C.c_char_p, _DP, C.POINTER(C.c_long)]),
     ("r360_ctx_timing_reset", C.c_int, [_P]),
+    ("r360_cloud_filter_euclidean", C.c_int, [_FP, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _FP, _P,
+                                              C.POINTER(C.c_size_t)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -1308,6 +1310,39 @@ def exp_se3(mu, pseudo: bool = True) -> np.ndarray:
     T = np.zeros(16, np.float32)
     lib().r360_exp_se3(m.ctypes.data_as(_DP), int(pseudo), _fptr(T))
     return _from16(T)
+
+
+def _cloud_arrays(xyz, rgba):
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    if rgba is not None:
+        rgba = np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+        assert rgba.shape[0] == xyz.shape[0]
+    return xyz, rgba
+
+
+def filter_euclidean(xyz, rgba=None, x_min: float = -2.0, x_max: float = 1.0, box: float = 4.0):
+    """FilterPointCloud::filterEuclidean on the host (r360_cloud_filter_euclidean, no GPU): the points with finite
+    coordinates inside [x_min, x_max] x [-box, box]^2, in order.  Returns (xyz [m,3], rgba [m] or None)."""
+    xyz, rgba = _cloud_arrays(xyz, rgba)
+    n = xyz.shape[0]
+    oxyz = np.zeros((n, 3), np.float32)
+    orgba = None if rgba is None else np.zeros(n, np.uint32)
+    m = C.c_size_t()
+    _check(lib().r360_cloud_filter_euclidean(_fptr(xyz), None if rgba is None else _vptr(rgba), n, x_min, x_max, box,
+                                             _fptr(oxyz), None if rgba is None else _vptr(orgba), C.byref(m)),
+           "filter_euclidean")
+    return oxyz[:m.value].copy(), None if rgba is None else orgba[:m.value].copy()
+
+
+class FilterPointCloud:
+    """FilterPointCloud (include/FilterPointCloud.h) with the reference's constructor defaults: filterEuclidean on
+    the host, returning (xyz, rgba).  (filterVoxel is not provided.)"""
+
+    def __init__(self, voxelSize: float = 0.05, euclideanBox: float = 4.0):
+        self.voxelSize, self.euclideanBox = voxelSize, euclideanBox
+
+    def filterEuclidean(self, xyz, rgba=None):
+        return filter_euclidean(xyz, rgba, -2.0, 1.0, self.euclideanBox)
 
 
 DATA_DIR = os.path.join(REPO_ROOT, "data")
