@@ -7,6 +7,8 @@
 // alignFrames360 refinement.  Graph optimisation, submaps and the viewer are out of scope.
 //   usage: SphereGraphTracking <dir with sphere_images_<n>.bin> [first] [step] [calib_dir]
 //          SphereGraphTracking --synthetic <n_frames>        (procedural room, 8 x 480x640, no I/O)
+//   either form may end in "--map FILE.pcd": the keyframes' clouds are fused into the context's device-resident
+//   global map (r360::GlobalMap360) and written to FILE.pcd at the end
 #include <rgbd360/rgbd360.h>
 
 #include <cmath>
@@ -28,8 +30,16 @@ static r360::Matrix4f inverse_rigid(const r360::Matrix4f& T) {
 }
 
 int main(int argc, char** argv) {
+    // optional trailing "--map FILE.pcd": every accepted keyframe's cloud goes into the context's global map with its
+    // pose (Euclidean box, pose, voxel grid of 5 cm: SphereGraphSLAM.cpp:116, :136-137, :193, :206-209)
+    std::string map_file;
+    if (argc >= 4 && std::string(argv[argc - 2]) == "--map") {
+        map_file = argv[argc - 1];
+        argc -= 2;
+    }
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s <dir> [first] [step] [calib_dir] | --synthetic <n_frames>\n", argv[0]);
+        std::fprintf(stderr, "usage: %s <dir> [first] [step] [calib_dir] | --synthetic <n_frames>  [--map FILE.pcd]\n",
+                     argv[0]);
         return 1;
     }
     const bool synthetic = std::string(argv[1]) == "--synthetic";
@@ -71,6 +81,7 @@ int main(int argc, char** argv) {
         std::vector<std::unique_ptr<r360::Frame360> > kfs;
         std::vector<r360::Matrix4f> poses;
         int n_lc = 0;
+        r360::GlobalMap360 globalMap(ctx);
         for (int idx = first;; idx += step) {
             std::unique_ptr<r360::Frame360> f(new r360::Frame360(&calib));
             if (!load(*f, idx)) break;
@@ -79,6 +90,7 @@ int main(int argc, char** argv) {
             if (kfs.empty()) {
                 kfs.push_back(std::move(f));
                 poses.push_back(r360::Matrix4f::Identity());
+                if (!map_file.empty()) globalMap.add(*kfs.back(), poses.back());
                 continue;
             }
             std::vector<r360::Frame360*> kf;
@@ -95,6 +107,7 @@ int main(int argc, char** argv) {
             std::printf("frame %d: Good TRACKING with keyframe %d, %d matches, SSO %.3f\n", idx, j, win.n_match,
                         win.sso_pbmap);
             kfs.push_back(std::move(f));
+            if (!map_file.empty()) globalMap.add(*kfs.back(), poses.back());
             if (int(kfs.size()) % lc_every == 0) {       // loop-closure candidates of the newest keyframe
                 std::vector<std::pair<r360::Frame360*, r360::Frame360*> > pairs;
                 std::vector<int> ids;
@@ -115,6 +128,13 @@ int main(int argc, char** argv) {
             }
         }
         std::printf("%zu keyframes, %d loop-closure edges\n", kfs.size(), n_lc);
+        if (!map_file.empty()) {
+            r360::PointCloud cloud;
+            globalMap.download(cloud);
+            r360::check(r360_pcd_write(map_file.c_str(), cloud.xyz.data(), cloud.rgba.data(), cloud.width, cloud.height, 1),
+                        "r360_pcd_write");
+            std::printf("global map: %zu points -> %s\n", cloud.size(), map_file.c_str());
+        }
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());
         return 2;

@@ -734,11 +734,15 @@ R360_NO_FP_CONTRACT inline void transformPointCloud(const PointCloud& in, PointC
 }
 
 // FilterPointCloud (include/FilterPointCloud.h) with the reference's constructor defaults: filterEuclidean works
-// on the cloud in place, on the host, and leaves it unorganised.  (filterVoxel is not provided.)
+// on the cloud in place, on the host, and leaves it unorganised; filterVoxel (pcl::VoxelGrid with leaf voxelSize)
+// runs on the GPU of the calling thread's default context, or of the Context given to the second constructor, and
+// leaves one point per occupied voxel in ascending (k, j, i) voxel order (r360_cloud_filter_voxel).
 class FilterPointCloud {
   public:
     FilterPointCloud(const float voxelSize = 0.05f, const float euclideanBox = 4.0f)
-        : box_(euclideanBox) { (void)voxelSize; }
+        : voxel_(voxelSize), box_(euclideanBox) {}
+    FilterPointCloud(Context& ctx, const float voxelSize = 0.05f, const float euclideanBox = 4.0f)
+        : ctx_(&ctx), voxel_(voxelSize), box_(euclideanBox) {}
     void filterEuclidean(PointCloud& cloud) {
         size_t n = 0;
         check(r360_cloud_filter_euclidean(cloud.xyz.data(), cloud.rgba.data(), cloud.size(), -2.0f, 1.0f, box_,
@@ -746,8 +750,58 @@ class FilterPointCloud {
               "filterEuclidean");
         cloud.resize(n);
     }
+    // false: PCL's size guard refused the leaf ("Leaf size is too small for the input dataset"), the cloud is unchanged
+    bool filterVoxel(PointCloud& cloud) {
+        size_t n = 0;
+        Context& c = ctx_ ? *ctx_ : default_context();
+        const int rc = check(r360_cloud_filter_voxel(c.get(), cloud.xyz.data(), cloud.rgba.data(), cloud.size(), voxel_,
+                                                     cloud.xyz.data(), cloud.rgba.data(), cloud.size(), &n),
+                             "filterVoxel");
+        if (rc == 0) cloud.resize(n);
+        return rc == 0;
+    }
+    float voxelSize() const { return voxel_; }
   private:
-    float box_;
+    Context* ctx_ = nullptr;
+    float voxel_, box_;
 };
+
+// A view of a context's global map (r360_ctx_map_*): `globalMap += cloud; filter.filterVoxel(globalMap)` of
+// SLAM/SphereGraphSLAM.cpp:136-137, :208-209 with the map resident in HBM.  The map belongs to the context and is
+// freed with it; the view owns nothing on the device (its destructor makes no GPU call) and keeps the default
+// context alive while it exists.
+class GlobalMap360 {
+  public:
+    explicit GlobalMap360(const float voxelSize = 0.05f, const float euclideanBox = 4.0f)
+        : keep_(default_context_ptr()), ctx_(keep_.get()), voxel_(voxelSize), box_(euclideanBox) {}
+    explicit GlobalMap360(Context& ctx, const float voxelSize = 0.05f, const float euclideanBox = 4.0f)
+        : ctx_(&ctx), voxel_(voxelSize), box_(euclideanBox) {}
+    void reset() { check(r360_ctx_map_reset(ctx_->get()), "GlobalMap360::reset"); }
+    // the whole map step on the keyframe's cloud in HBM: filterEuclidean, transformPointCloud(pose), +=, filterVoxel
+    bool add(Frame360& keyframe, const Matrix4f& pose);
+    // globalMap += cloud; filterVoxel(globalMap)
+    bool add(const PointCloud& cloud) {
+        return check(r360_ctx_map_add_cloud(ctx_->get(), cloud.xyz.data(), cloud.rgba.data(), cloud.size(), voxel_),
+                     "GlobalMap360::add") == 0;
+    }
+    size_t size() const {
+        size_t n = 0;
+        check(r360_ctx_map_size(ctx_->get(), &n), "GlobalMap360::size");
+        return n;
+    }
+    void download(PointCloud& cloud) const {
+        size_t n = size();
+        cloud.resize(n);
+        check(r360_ctx_map_download(ctx_->get(), cloud.xyz.data(), cloud.rgba.data(), n, &n), "GlobalMap360::download");
+    }
+  private:
+    std::shared_ptr<Context> keep_;
+    Context* ctx_;
+    float voxel_, box_;
+};
+inline bool GlobalMap360::add(Frame360& keyframe, const Matrix4f& pose) {
+    return check(r360_ctx_map_add_frame(ctx_->get(), keyframe.get(), pose.data(), -2.0f, 1.0f, box_, voxel_),
+                 "GlobalMap360::add") == 0;
+}
 
 }  // namespace r360

@@ -637,6 +637,39 @@ int r360_ctx_kernel_time_reset(r360_ctx* ctx);
 int r360_cloud_filter_euclidean(const float* xyz, const uint32_t* rgba, size_t n, float x_min, float x_max, float box,
                                 float* out_xyz, uint32_t* out_rgba, size_t* n_out);
 
+/* FilterPointCloud::filterVoxel (pcl::VoxelGrid with leaf size `leaf` on all axes, restated from PCL 1.7) on ctx's GPU.
+ * Non-finite points are dropped; with inv = 1.0f / leaf the voxel of a point is (int)floorf(x * inv) per axis; each
+ * occupied voxel gives one point: xyz the mean of its points, r / g / b the integer floor of the channel means,
+ * alpha 0; a voxel holding exactly one point gives that point's xyz bits unchanged.  The output is in ascending
+ * (k, j, i) voxel order, the same from run to run and for any order of the input.  Means are formed from 64-bit integer
+ * sums of llrint(coordinate / R360_VOXEL_QUANTUM): each lies within R360_VOXEL_QUANTUM / 2 + half a float ulp of
+ * the exact mean.
+ * Returns 1, with the output equal to the input (n points), when PCL's size guard refuses the leaf ("Leaf size is too
+ * small for the input dataset"): with min / max the bounds of the finite points and d = (int64)((max - min) * inv) + 1
+ * per axis in float, dx * dy * dz > INT32_MAX (or the grid from floor(min * inv) to floor(max * inv) has more cells).
+ * Supported domain: ceil(max |coordinate|) * 2^24 * (finite points) < 2^62 (so 1024 m with 2^27 points, 8192 m
+ * with 2^24) and |voxel index| < 2^30; outside it the call fails (< 0), as it does for n > 2^30.
+ * rgba / out_rgba may be NULL; the outputs may be the inputs; cap = room in the outputs: cap < *n_out is an error
+ * (< 0) that still sets *n_out. */
+#define R360_VOXEL_QUANTUM (1.0 / 16777216.0)   /* 2^-24 m */
+int r360_cloud_filter_voxel(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n, float leaf,
+                            float* out_xyz, uint32_t* out_rgba, size_t cap, size_t* n_out);
+
+/* The context's global map (globalMap of SLAM/SphereGraphSLAM.cpp): device-resident, one per context, empty at first,
+ * owned by the context and freed by r360_ctx_destroy.  add_cloud: map <- voxel grid of (map ++ cloud), bit for bit
+ * r360_cloud_filter_voxel of the concatenated arrays.  add_frame: the whole map step on the frame's clouds in HBM
+ * (built with R360_BUILD_CLOUD): Rt_[sensor], the Euclidean box (r360_cloud_filter_euclidean), pose (column-major
+ * 4x4, m(k,0)*x + m(k,1)*y + m(k,2)*z + m(k,3) in float, left to right), then add_cloud's step; a frame whose
+ * sphereCloud was loaded (r360_frame_load_cloud) takes the same steps from that cloud.  The frame may belong to another
+ * context of the same device.  A soft failure (1, the size guard) or an error leaves the map as it was.
+ * download: cap < the map's size is an error (< 0); *n is set either way; xyz and rgba NULL: only *n. */
+int r360_ctx_map_reset(r360_ctx* ctx);
+int r360_ctx_map_add_cloud(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n, float leaf);
+int r360_ctx_map_add_frame(r360_ctx* ctx, r360_frame* f, const float pose[16], float x_min, float x_max, float box,
+                           float leaf);
+int r360_ctx_map_size(r360_ctx* ctx, size_t* n);
+int r360_ctx_map_download(r360_ctx* ctx, float* xyz, uint32_t* rgba, size_t cap, size_t* n);
+
 #ifdef __cplusplus
 }
 #endif

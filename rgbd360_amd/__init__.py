@@ -291,6 +291,13 @@ _SIGS = [
     ("r360_ctx_timing_reset", C.c_int, [_P]),
     ("r360_cloud_filter_euclidean", C.c_int, [_FP, _P, C.c_size_t, C.c_float, C.c_float, C.c_float, _FP, _P,
                                               C.POINTER(C.c_size_t)]),
+    ("r360_cloud_filter_voxel", C.c_int, [_P, _FP, _P, C.c_size_t, C.c_float, _FP, _P, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
+    ("r360_ctx_map_reset", C.c_int, [_P]),
+    ("r360_ctx_map_add_cloud", C.c_int, [_P, _FP, _P, C.c_size_t, C.c_float]),
+    ("r360_ctx_map_add_frame", C.c_int, [_P, _P, _FP, C.c_float, C.c_float, C.c_float, C.c_float]),
+    ("r360_ctx_map_size", C.c_int, [_P, C.POINTER(C.c_size_t)]),
+    ("r360_ctx_map_download", C.c_int, [_P, _FP, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -429,6 +436,51 @@ class Context:
         a, b, c = C.c_long(), C.c_long(), C.c_long()
         _check(lib().r360_ctx_match_stats(self.h, C.byref(a), C.byref(b), C.byref(c)), "match_stats")
         return a.value, b.value, c.value
+
+    def filter_voxel(self, xyz, rgba=None, leaf: float = 0.05):
+        """FilterPointCloud::filterVoxel on this context's GPU (r360_cloud_filter_voxel): one point per occupied voxel
+        of size `leaf`, in ascending (k, j, i) voxel order.  Returns (xyz [m,3], rgba [m] or None, ok); ok is False
+        when PCL's size guard refuses the leaf, and the cloud then comes back unchanged."""
+        xyz, rgba = _cloud_arrays(xyz, rgba)
+        n = xyz.shape[0]
+        oxyz = np.zeros((n, 3), np.float32)
+        orgba = None if rgba is None else np.zeros(n, np.uint32)
+        m = C.c_size_t()
+        rc = _check(lib().r360_cloud_filter_voxel(self.h, _fptr(xyz), None if rgba is None else _vptr(rgba), n, leaf,
+                                                  _fptr(oxyz), None if rgba is None else _vptr(orgba), n, C.byref(m)),
+                    "filter_voxel")
+        return oxyz[:m.value].copy(), None if rgba is None else orgba[:m.value].copy(), rc == 0
+
+    def map_reset(self):
+        """Empties the context's global map."""
+        _check(lib().r360_ctx_map_reset(self.h), "map_reset")
+
+    def map_add_cloud(self, xyz, rgba=None, leaf: float = 0.05) -> bool:
+        """globalMap += cloud; filterVoxel(globalMap) on the device-resident map.  False: the size guard refused the
+        leaf and the map is as it was."""
+        xyz, rgba = _cloud_arrays(xyz, rgba)
+        return _check(lib().r360_ctx_map_add_cloud(self.h, _fptr(xyz), None if rgba is None else _vptr(rgba),
+                                                   xyz.shape[0], leaf), "map_add_cloud") == 0
+
+    def map_add_frame(self, frame, pose, leaf: float = 0.05, box: float = 4.0, x_min: float = -2.0,
+                      x_max: float = 1.0) -> bool:
+        """The map step on a frame's cloud in HBM (built with BUILD_CLOUD): Euclidean box in the rig frame, `pose`
+        (4x4), append, voxel grid."""
+        return _check(lib().r360_ctx_map_add_frame(self.h, frame.h, _fptr(_mat16(pose)), x_min, x_max, box, leaf),
+                      "map_add_frame") == 0
+
+    def map_size(self) -> int:
+        n = C.c_size_t()
+        _check(lib().r360_ctx_map_size(self.h, C.byref(n)), "map_size")
+        return n.value
+
+    def map_download(self):
+        """The map as (xyz [n,3] f32, rgba [n] u32), in ascending voxel order."""
+        n = C.c_size_t(self.map_size())
+        xyz = np.zeros((n.value, 3), np.float32)
+        rgba = np.zeros(n.value, np.uint32)
+        _check(lib().r360_ctx_map_download(self.h, _fptr(xyz), _vptr(rgba), n.value, C.byref(n)), "map_download")
+        return xyz, rgba
 
     def close(self):
         if self.h:
@@ -1336,13 +1388,23 @@ def filter_euclidean(xyz, rgba=None, x_min: float = -2.0, x_max: float = 1.0, bo
 
 class FilterPointCloud:
     """FilterPointCloud (include/FilterPointCloud.h) with the reference's constructor defaults: filterEuclidean on
-    the host, returning (xyz, rgba).  (filterVoxel is not provided.)"""
+    the host, returning (xyz, rgba); filterVoxel on the GPU of `ctx`, returning (xyz, rgba) one point per voxel of
+    voxelSize (the cloud unchanged when PCL's size guard refuses the leaf)."""
 
-    def __init__(self, voxelSize: float = 0.05, euclideanBox: float = 4.0):
-        self.voxelSize, self.euclideanBox = voxelSize, euclideanBox
+    def __init__(self, voxelSize: float = 0.05, euclideanBox: float = 4.0, ctx: "Context | None" = None):
+        self.voxelSize, self.euclideanBox, self.ctx = voxelSize, euclideanBox, ctx
 
     def filterEuclidean(self, xyz, rgba=None):
         return filter_euclidean(xyz, rgba, -2.0, 1.0, self.euclideanBox)
+
+    def filterVoxel(self, xyz, rgba=None):
+        if self.ctx is None:
+            raise RuntimeError("FilterPointCloud.filterVoxel runs on a GPU: construct the filter with ctx=Context(...)")
+        oxyz, orgba, _ = self.ctx.filter_voxel(xyz, rgba, self.voxelSize)
+        return oxyz, orgba
+
+
+VOXEL_QUANTUM = 2.0 ** -24   # R360_VOXEL_QUANTUM: the fixed-point unit (m) of the voxel grid's coordinate sums
 
 
 DATA_DIR = os.path.join(REPO_ROOT, "data")

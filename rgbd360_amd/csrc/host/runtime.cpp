@@ -307,6 +307,7 @@ extern "C" void r360_ctx_destroy(r360_ctx* c) {
     hipFree(c->d_match_desc); hipFree(c->d_unary); hipFree(c->d_bin); hipFree(c->d_vhash);
     hipFree(c->d_vlist); hipFree(c->d_vcnt);
     for (auto& s : c->bvox) vox_slot_free(s);
+    map_state_free(c->vmap);   // voxel-filter scratch and the context's global map
     hipHostFree(c->h_unary); hipHostFree(c->h_bin);
     if (c->up_stream) {
         hipStreamSynchronize(c->up_stream);

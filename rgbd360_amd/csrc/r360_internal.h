@@ -296,10 +296,69 @@ struct PlaneDev {
 struct PlaneBatch { PlaneDev f[R360_PLANE_BATCH]; };
 static_assert(sizeof(PlaneBatch) + 256 <= 4096, "the plane batch travels as a kernel argument");
 
+// ------------------------------------------------------------------ voxel grid / global map
+// (kernels/map_kernels.hip, host/map.cpp)
+// A point travels as 16 bytes: the bits of x, y, z and the PointXYZRGBA-packed colour.
+// One cell of the open-addressing voxel table, all zero when empty.  Coordinate sums are 64-bit two's-complement
+// integers in units of R360_VOXEL_QUANTUM (2^-24 m), colour sums exact integers: no sum depends on arrival order.
+struct alignas(16) MapCell {
+    unsigned key1;               // linear voxel index + 1 (0 = empty), claimed by atomicCAS
+    unsigned cnt;
+    unsigned idx;                // the claiming point's index in the input list (the singleton rule reads it back)
+    unsigned pad;
+    unsigned long long s[3];     // sum of llrint(coordinate * 2^24)
+    unsigned long long c[3];     // sums of r, g, b
+};
+static_assert(sizeof(MapCell) == 64, "the finalise pass zeroes a cell as four 16-byte stores");
+// bounds of the finite points (floats as order-preserving unsigned), their count, the occupied voxels, error bits
+struct MapHdr { unsigned mn[3], mx[3]; unsigned long long count; unsigned m, err, pad[2]; };
+struct MapGrid { float inv; int minb[3]; unsigned dx, dy; };   // dx, dy: the grid's extent in voxels along x and y
+struct MapRig { float rt[8][16]; };                            // Rt_[sensor], column-major (a kernel argument)
+struct MapPose { float m[16]; };
+constexpr size_t R360_MAP_SCAN_BLOCK = 2048;                   // bitmap words per workgroup of the popcount scan
+// Everything the voxel filter and the context's map hold on the device: plain pointers owned by the r360_ctx and
+// freed by map_state_free from r360_ctx_destroy.
+struct MapState {
+    MapHdr* d_hdr = nullptr;
+    MapHdr* h_hdr = nullptr;             // pinned
+    MapCell* table = nullptr;            // all cells zero between calls
+    size_t table_cap = 0;
+    unsigned* list = nullptr;            // [table_cap / 2] cells claimed by the running call
+    size_t list_cap = 0;
+    unsigned* bitmap = nullptr;          // occupancy of the bounding grid, one bit per voxel
+    unsigned* wprefix = nullptr;         // exclusive prefix of the bitmap words' popcounts
+    size_t bitmap_cap = 0, wprefix_cap = 0;
+    unsigned* bsum = nullptr;            // per-workgroup popcounts of the scan
+    size_t bsum_cap = 0;
+    float* up_xyz = nullptr;             // staging of host arrays: up_xyz_cap floats, up_rgba_cap colours
+    uint32_t* up_rgba = nullptr;
+    size_t up_xyz_cap = 0, up_rgba_cap = 0;
+    uint4* in = nullptr;                 // r360_cloud_filter_voxel's packed input and output
+    uint4* out = nullptr;
+    size_t in_cap = 0, out_cap = 0;
+    uint4* map[2] = {nullptr, nullptr};  // the context's map: map[cur][0 .. map_n), the other buffer takes the next result
+    size_t map_cap[2] = {0, 0};
+    size_t map_n = 0;
+    int cur = 0;
+};
+void map_state_free(MapState& M);
+int launch_map_pack_host(hipStream_t st, const float* xyz, const uint32_t* rgba, size_t n, uint4* out);
+int launch_map_pack_frame(hipStream_t st, const float4* cloud, const uchar4* rgb, size_t per_sensor, const MapRig& rig,
+                          const MapPose& pose, float x_min, float x_max, float box, uint4* out);
+int launch_map_bounds(hipStream_t st, const uint4* pts, size_t n, MapHdr* hdr);
+int launch_map_insert(hipStream_t st, const uint4* pts, size_t n, const MapGrid& G, MapCell* table, size_t table_cap,
+                      unsigned* bitmap, unsigned* list, MapHdr* hdr);
+int launch_map_scan(hipStream_t st, const unsigned* bitmap, size_t nwords, unsigned* bsum, unsigned* wprefix);
+int launch_map_finalise(hipStream_t st, const uint4* pts, size_t n, MapCell* table, size_t table_cap,
+                        const unsigned* list, const unsigned* bitmap, size_t nwords, const unsigned* wprefix, MapHdr* hdr,
+                        uint4* out, size_t out_cap);
+int launch_map_unpack(hipStream_t st, const uint4* pts, size_t m, float* xyz, uint32_t* rgba);
+
 // ------------------------------------------------------------------ host objects
 struct r360_plane_queue;
 struct VoxSlot;
 struct r360_ctx {
+    MapState vmap;                         // voxel-filter scratch and the context's global map (host/map.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
     hipStream_t stream = nullptr;
