@@ -73,6 +73,12 @@ enum {
     R360_BUILD_CLOUD     = 1u << 3,  /* Frame360::buildSphereCloud()     Frame360.h:467   */
     R360_BUILD_PLANES    = 1u << 4,  /* Frame360::getPlanes()            Frame360.h:615   */
     R360_BUILD_SENSOR_PYRAMID = 1u << 5, /* per-sensor setSource/TargetFrame (pinhole alignFrames) */
+    /* Reported by r360_frame_built only (not a stage to ask for): the sphere images and level 0's {gray, depth}
+     * image are in HBM.  Clear after the build of a frame that only enters batched alignments
+     * (r360_frame_set_compaction(f, 0)) where those passes stream level 0's packed image: such a build writes
+     * only that; the first call that reads one of the others (r360_frame_get_sphere, level 0 of
+     * r360_frame_get_level / _get_points, a lone or occlusion alignment) stitches again in full and sets it. */
+    R360_BUILT_LEVEL0 = 1u << 8,
 };
 int  r360_frame_create(r360_ctx* ctx, const r360_calib* calib, r360_frame** out);
 void r360_frame_destroy(r360_frame* f);
@@ -116,7 +122,8 @@ int  r360_frame_set_levels(r360_frame* f, int n);
  * fewer, for frames that only enter batched alignments, e.g. a dense queue's); a lone alignment then streams the
  * images too.  Poses are equal to rounding either way.  Takes effect at the next build. */
 int  r360_frame_set_compaction(r360_frame* f, int all);
-/* The R360_BUILD_* stages the frame's current images have been through (an upload or load clears them). */
+/* The R360_BUILD_* stages the frame's current images have been through (an upload or load clears them), and
+ * R360_BUILT_LEVEL0. */
 int  r360_frame_built(const r360_frame* f, unsigned* flags);
 /* sphereRGB (BGR u8) / sphereDepth (u16 range mm) (Frame360.h:104-107). */
 int  r360_frame_get_sphere(r360_frame* f, uint8_t* bgr, uint16_t* depth);

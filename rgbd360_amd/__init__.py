@@ -36,6 +36,7 @@ REPO_ROOT = os.path.dirname(_HERE)
 PHOTO_CONSISTENCY, DEPTH_CONSISTENCY, PHOTO_DEPTH = 0, 1, 2
 BUILD_UNDISTORT, BUILD_SPHERE, BUILD_PYRAMID, BUILD_CLOUD, BUILD_PLANES = 1, 2, 4, 8, 16
 BUILD_SENSOR_PYRAMID = 32
+BUILT_LEVEL0 = 256   # reported by Frame360.built() only: the sphere images and level 0's {gray, depth} are in HBM
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2
 
 
@@ -679,6 +680,12 @@ class Frame360:
     def build(self, flags: int = BUILD_UNDISTORT | BUILD_SPHERE | BUILD_PYRAMID, sync: bool = True):
         fn = lib().r360_frame_build if sync else lib().r360_frame_build_async
         _check(fn(self.h, flags), "r360_frame_build")
+
+    def built(self) -> int:
+        """r360_frame_built: the BUILD_* stages done, and BUILT_LEVEL0."""
+        u = C.c_uint()
+        _check(lib().r360_frame_built(self.h, C.byref(u)), "r360_frame_built")
+        return u.value
 
     def undistort(self):
         self.build(BUILD_UNDISTORT)

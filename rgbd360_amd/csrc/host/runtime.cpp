@@ -761,6 +761,7 @@ extern "C" int r360_frame_set_sphere(r360_frame* f, const uint8_t* bgr, const ui
     const size_t n = (size_t)sph_rows * sph_cols;
     R360_HIP(hipMemcpyAsync(f->d_sph_bgr, bgr, n * 3, hipMemcpyHostToDevice, f->ctx->stream));
     R360_HIP(hipMemcpyAsync(f->d_sph_depth, range_mm, n * 2, hipMemcpyHostToDevice, f->ctx->stream));
+    f->built |= R360_BUILT_LEVEL0;   // the given sphere and its level 0 in full (never stitched again over them)
     if (launch_sphere_level0(f) || launch_pyramid(f) || frame_build_event_record(f)) return -1;
     R360_HIP(hipStreamSynchronize(f->ctx->stream));
     f->built = (f->built & ~(unsigned)(R360_BUILD_SPHERE | R360_BUILD_PYRAMID)) | R360_BUILD_SPHERE | R360_BUILD_PYRAMID;
@@ -803,7 +804,10 @@ extern "C" int r360_frame_build_async(r360_frame* f, unsigned flags) {
         f->sphere_cloud = nullptr;
     }
     if (flags & (R360_BUILD_SPHERE | R360_BUILD_PYRAMID)) {
-        if (launch_stitch(f)) return -1;
+        const bool lean = frame_level0_lean(f);
+        if (launch_stitch(f, lean)) return -1;
+        if (lean) f->built &= ~(unsigned)R360_BUILT_LEVEL0;
+        else f->built |= R360_BUILT_LEVEL0;
         f->built |= R360_BUILD_SPHERE;
     }
     if (flags & R360_BUILD_PYRAMID) {
@@ -815,6 +819,18 @@ extern "C" int r360_frame_build_async(r360_frame* f, unsigned flags) {
         if (launch_sensor_pyramid(f)) return -1;
         f->built |= R360_BUILD_SENSOR_PYRAMID;
     }
+    return 0;
+}
+
+int frame_level0_materialise(r360_frame* f) {
+    const unsigned b = f->built.load();
+    // nothing to do for a full frame; a frame without a built sphere is refused by its reader's own check
+    if ((b & R360_BUILT_LEVEL0) || !(b & R360_BUILD_SPHERE) || f->rows <= 0) return 0;
+    if (bind_device(f->ctx->device)) return -1;
+    if (launch_stitch(f, false)) return -1;
+    // waited for: the reader may run on another context's stream (an alignment of frames built elsewhere)
+    R360_HIP(hipStreamSynchronize(f->ctx->stream));
+    f->built |= R360_BUILT_LEVEL0;
     return 0;
 }
 
@@ -862,6 +878,7 @@ extern "C" int r360_frame_built(const r360_frame* f, unsigned* flags) {
 extern "C" int r360_frame_get_sphere(r360_frame* f, uint8_t* bgr, uint16_t* depth) {
     CHECK_ARG(f, "null frame");
     CHECK_ARG(f->built & R360_BUILD_SPHERE, "sphere not built");
+    if (frame_level0_materialise(f)) return -1;
     const size_t n = (size_t)f->sph_rows * f->sph_cols;
     R360_HIP(hipStreamSynchronize(f->ctx->stream));
     if (bgr) R360_HIP(hipMemcpy(bgr, f->d_sph_bgr, n * 3, hipMemcpyDeviceToHost));
@@ -903,6 +920,7 @@ extern "C" int r360_frame_get_level(r360_frame* f, int level, int* rows, int* co
     CHECK_ARG(f, "null frame");
     CHECK_ARG(level >= 0 && level < f->n_levels, "level out of range");
     CHECK_ARG(f->built & R360_BUILD_PYRAMID, "pyramid not built");
+    if (level == 0 && frame_level0_materialise(f)) return -1;
     const LevelBufs& L = f->lv[level];
     return copy_level(f, L.p0, L.tg, L.rows, L.cols, rows, cols, gray, depth, gx, gy, dgx, dgy);
 }
@@ -981,6 +999,15 @@ static int check_pair(r360_ctx* ctx, r360_frame* trg, r360_frame* src, const r36
               "non-default min/max depth changes the depth pyramid: not supported in this version");
     CHECK_ARG(ctx->partials_cap >= icp_blocks_for(src->lv[0].rows * src->lv[0].cols), "partials buffer too small");
     return 0;
+}
+
+// Before the level-0 passes of an alignment are enqueued: every form but the packed-image pass (PF 6) reads level 0's
+// {gray, depth} image of the target, the source or both (PF 5 the target's, PF 3 / PF 0 and the occlusion projection
+// both), which a lean frame (frame_level0_lean) has not written yet.
+static int pair_level0_ready(r360_ctx* ctx, r360_frame* trg, r360_frame* src, int occ, bool batched) {
+    if (icp_pass_form(ctx, src, 0, occ, batched) == 6) return 0;
+    if (frame_level0_materialise(trg) || frame_level0_materialise(src)) return -1;
+    return bind_device(ctx->device);
 }
 
 // Replays the captured pass sequence of (trg, src, method, p) on ctx's stream, capturing it on first use.  The key
@@ -1072,6 +1099,7 @@ extern "C" int r360_align360_async(r360_ctx* ctx, r360_frame* trg, r360_frame* s
     CHECK_ARG(init, "null init pose");
     CHECK_ARG(method >= 0 && method <= 2, "invalid method");
     CHECK_ARG(occlusion >= 0 && occlusion <= 2, "occlusion must be 0, 1 or 2");
+    if (pair_level0_ready(ctx, trg, src, occlusion, false)) return -1;
     if (ensure_defer(ctx, src->lv[0].rows * src->lv[0].cols)) return -1;
     // frames built on another context (another thread's): this stream waits for their pyramid builds
     for (const r360_frame* f : {trg, src})
@@ -1219,6 +1247,8 @@ int align360_batch_enqueue(r360_ctx* ctx, int n, r360_frame* const* trg, r360_fr
         CHECK_ARG(src[j]->sph_rows == src[0]->sph_rows && src[j]->sph_cols == src[0]->sph_cols,
                   "batched alignments need frames of one sphere size");
     }
+    for (int j = 0; j < n; ++j)   // a no-op where level 0 runs PF 6 (the dense queue's frames)
+        if (pair_level0_ready(ctx, trg[j], src[j], 0, true)) return -1;
     if (ensure_batch(ctx, n, (long)src[0]->lv[0].rows * src[0]->lv[0].cols)) return -1;
     std::vector<r360_frame*> fr;
     for (int j = 0; j < n; ++j) { fr.push_back(trg[j]); fr.push_back(src[j]); }
@@ -1296,6 +1326,7 @@ static int icp_eval_sums(r360_ctx* ctx, r360_frame* trg, r360_frame* src, int le
     CHECK_ARG(level >= 0 && level < src->n_levels, "level out of range");
     CHECK_ARG(method >= 0 && method <= 2, "invalid method");
     CHECK_ARG(occ >= 0 && occ <= 2, "occlusion must be 0, 1 or 2");
+    if (level == 0 && pair_level0_ready(ctx, trg, src, occ, false)) return -1;
     if (ensure_defer(ctx, src->lv[level].rows * src->lv[level].cols)) return -1;
     IcpState* h = ctx->h_state;
     memset(h, 0, sizeof(IcpState));

@@ -5,7 +5,8 @@
 //   k_pyramid   : pyrDown (gray) + buildPyramidRange (depth)  (RegisterPhotoICP.h:292-354)
 //   k_gradient  : calcGradientXY for gray and depth + the alignFrames360 seam mask
 //                 (RegisterPhotoICP.h:365-398, 4538-4549)
-// All are HBM-streaming, one thread per output pixel.  Compiled with -ffp-contract=off so each
+//   k_prep_l0, k_prep_tail : the sphere's pyramid and gradients, the two above tiled through LDS
+// All but the last two are HBM-streaming, one thread per output pixel.  Compiled with -ffp-contract=off so each
 // float expression rounds exactly as the reference's scalar C++ does.
 #include "../r360_internal.h"
 
@@ -209,7 +210,10 @@ __global__ void k_stitch4(const uint8_t* __restrict__ bgr8, const uint16_t* __re
 // of BGR bytes and ranges read a few consecutive cache lines of one sensor row, where k_stitch4's row-major waves read
 // 64 sensor rows (a line per byte).  The tile goes through LDS and is stored row-major as k_stitch4 stores it.  Per
 // pixel the expressions of k_stitch (the sensor pose loaded once per column, which is one sensor), bit for bit.
+// LEAN: only the packed level-0 image is stored (4 of the 17 bytes per pixel), for frames whose other level-0
+// outputs no kernel reads (frame_level0_lean; the full form runs again if one is asked for).
 constexpr int STT_R = 64, STT_C = 16;
+template <bool LEAN>
 __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bgr8, const uint16_t* __restrict__ depth8,
                                                   int rows, int cols, int H, int W, const float* __restrict__ sinphi,
                                                   const float* __restrict__ cosphi, const float* __restrict__ sinth,
@@ -218,7 +222,7 @@ __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bg
                                                   uint16_t* __restrict__ sph_depth, float2* __restrict__ p0,
                                                   uint32_t* __restrict__ pk) {
     __shared__ uint32_t s_pk[STT_C][STT_R + 1];    // range mm | luma << 16
-    __shared__ uint32_t s_bgr[STT_C][STT_R + 1];   // b | g << 8 | r << 16
+    __shared__ uint32_t s_bgr[LEAN ? 1 : STT_C][STT_R + 1];   // b | g << 8 | r << 16
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int tiles_x = W / STT_C;
     const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
@@ -249,7 +253,7 @@ __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bg
         }
         const unsigned y = (b * 4899 + g * 9617 + r * 1868 + (1 << 13)) >> 14;
         s_pk[cl][lane] = dd | (y << 16);
-        s_bgr[cl][lane] = b | (g << 8) | (r << 16);
+        if (!LEAN) s_bgr[cl][lane] = b | (g << 8) | (r << 16);
     }
     __syncthreads();
     // row-major stores: thread t writes 4 consecutive pixels of tile row t / 4
@@ -259,8 +263,11 @@ __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bg
     const long i0 = (long)grow * W + tx * STT_C + c0;
     unsigned pk4[4], px[12];
 #pragma unroll
+    for (int e = 0; e < 4; ++e) pk4[e] = s_pk[c0 + e][tr];
+    *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
+    if (LEAN) return;
+#pragma unroll
     for (int e = 0; e < 4; ++e) {
-        pk4[e] = s_pk[c0 + e][tr];
         const unsigned q = s_bgr[c0 + e][tr];
         px[3 * e] = q & 255; px[3 * e + 1] = (q >> 8) & 255; px[3 * e + 2] = q >> 16;
     }
@@ -277,7 +284,6 @@ __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bg
         o[e] = make_float2((float)(pk4[e] >> 16) * (float)(1. / 255), (float)(pk4[e] & 0xffffu) * 0.001f);
     *reinterpret_cast<float4*>(p0 + i0) = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
     *reinterpret_cast<float4*>(p0 + i0 + 2) = make_float4(o[2].x, o[2].y, o[3].x, o[3].y);
-    *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
 }
 
 __device__ __forceinline__ int refl101(int p, int n) {
@@ -293,9 +299,18 @@ struct LvF2 {
     __device__ __forceinline__ float g(long i) const { return p[i].x; }
     __device__ __forceinline__ float d(long i) const { return p[i].y; }
     __device__ __forceinline__ float2 gd(long i) const { return p[i]; }
+    // a pixel as it is kept in LDS, and its {gray, depth}
+    typedef float2 cell;
+    __device__ __forceinline__ cell raw(long i) const { return p[i]; }
+    static __device__ __forceinline__ float2 val(cell v) { return v; }
 };
 struct LvPk {
     const uint32_t* p;
+    typedef uint32_t cell;
+    __device__ __forceinline__ cell raw(long i) const { return p[i]; }
+    static __device__ __forceinline__ float2 val(cell v) {
+        return make_float2((float)(v >> 16) * (float)(1. / 255), (float)(v & 0xffffu) * 0.001f);
+    }
     __device__ __forceinline__ float g(long i) const { return (float)(p[i] >> 16) * (float)(1. / 255); }
     __device__ __forceinline__ float d(long i) const { return (float)(p[i] & 0xffffu) * 0.001f; }
     __device__ __forceinline__ float2 gd(long i) const {
@@ -376,57 +391,237 @@ __global__ void k_gradient(const float2* __restrict__ p0, int R, int C, float4* 
     }
 }
 
-// all sphere levels' gradients in one launch (the levels are independent once the pyramid is built): block b
-// belongs to the level l with blk0[l] <= b < blk0[l + 1], one pixel per thread
-struct GradLevels {
-    const float2* p0[R360_MAX_PYR];
-    const uint32_t* pk0;   // level 0's packed image (read instead of p0[0] when set)
-    float4* tg[R360_MAX_PYR];
-    int rows[R360_MAX_PYR], cols[R360_MAX_PYR];
-    int blk0[R360_MAX_PYR + 1];
-    int nl;
-};
+// ------------------------------------------------------------------ the sphere's pyramid and gradients, tiled
+// The sphere's levels and their gradients in two launches (three for a 6-level pyramid) instead of one per level
+// plus one for the gradients: a workgroup stages its tile with the halo the coarser levels need in LDS and builds
+// from there every output that depends on it.  Per pixel the expressions of k_pyramid and k_gradient (seam mask on),
+// on the same inputs: the horizontal 5-tap sum is computed once per (source row, output column) instead of once per
+// output pixel, which is the same float expression.
+__device__ __forceinline__ bool grad_live(int r, int c, int R, int C) {
+    const int ws = C / 8;   // >= 1: calib_build_tables stops the pyramid before a level narrower than 8
+    const int m = ws > 0 ? c % ws : 1;   // seam columns as k_gradient (alignFrames360 :4538-4549)
+    const bool seam = ws > 0 && (c >= ws - 1) && (c < 7 * ws + 1) && (m == 0 || m == ws - 1);
+    return !seam && r >= 1 && r < R - 1 && c >= 1 && c < C - 1;
+}
 
-// GRAD_PPT pixels per thread: a wave covers GRAD_PPT x 64 consecutive pixels, pixel k of a lane at i0 + 64 k (every
-// load and store coalesced across the wave); the row and column of the first pixel come from one 32-bit division and
-// are stepped by 64 columns for the others (one level search and one division per 4 pixels instead of per pixel:
-// in the pipeline the launch had 12.8 k single-pixel-per-thread workgroups per frame)
-constexpr int GRAD_PPT = 4;
+__device__ __forceinline__ float4 grad_of(float2 f, float2 fl, float2 fr, float2 fu, float2 fd) {
+    return make_float4(harm(fl.x, f.x, fr.x), harm(fu.x, f.x, fd.x), harm(fl.y, f.y, fr.y), harm(fu.y, f.y, fd.y));
+}
+
+// k_pyramid's vertical combination of the five row sums, and its 2x2 depth mean
+__device__ __forceinline__ float pyr_gray(float h0, float h1, float h2, float h3, float h4) {
+    float t0 = h0 + h4;
+    const float t1 = (h1 + h3) + h2;
+    t0 = t0 + (h2 + h2);
+    t0 = t0 + t1 * 4.f;
+    return t0 * (1.f / 256);
+}
+__device__ __forceinline__ float pyr_depth(float z0, float z1, float z2, float z3, float min_d, float max_d) {
+    float av = 0.f; unsigned nv = 0;
+    if (z0 > min_d && z0 < max_d) { av += z0; ++nv; }
+    if (z1 > min_d && z1 < max_d) { av += z1; ++nv; }
+    if (z2 > min_d && z2 < max_d) { av += z2; ++nv; }
+    if (z3 > min_d && z3 < max_d) { av += z3; ++nv; }
+    return nv > 0 ? av / nv : 0.f;
+}
+
+__device__ __forceinline__ int clampi(int p, int n) { return p < 0 ? 0 : (p >= n ? n - 1 : p); }
+
+// Launch 1: one workgroup per L0_TR x L0_TC tile of level 0 writes the tile's level-0 gradients, its level-1 pixels
+// and their gradients.  LDS cell (r, c) of s0 holds the level-0 pixel at refl101 of (y0 - 4 + r, x0 - 4 + c), the
+// border rule of k_pyramid on global coordinates (a level-1 pixel's taps reach 2 rows / columns past the image at
+// most; cells further out are clamped into the image and never used).  The halo of 4 supplies the ring of level-1
+// pixels around the tile's own (their taps: 2 (y - 1) - 2 = 2 y - 4), recomputed here for the level-1 gradients.
+// LDS: 24 x 136 x 4 (the packed image; x 8 from a float2 image) + 23 x 66 x 4 + 10 x 66 x 8 = 24.4 KB static: six
+// workgroups per CU, so the 1200 of a VGA sphere are resident at once (at 8 B per cell it took two rounds).
+constexpr int L0_TR = 16, L0_TC = 128, L0_HALO = 4;
+constexpr int L0_SR = L0_TR + 2 * L0_HALO, L0_SC = L0_TC + 2 * L0_HALO;   // staged level-0 cells
+constexpr int L0_1R = L0_TR / 2 + 2, L0_1C = L0_TC / 2 + 2;               // level-1 pixels: the tile's and a ring of 1
+constexpr int L0_HR = 2 * L0_1R + 3;                                      // source rows under them
 
 template <class IN>
-__device__ __forceinline__ void gradient_run(const IN p0, int i0, int R, int C, float4* __restrict__ tg) {
-    const int ws = C / 8;   // >= 1: calib_build_tables stops the pyramid before a level narrower than 8
-    const int n = R * C;
-    int r = i0 / C, c = i0 - r * C;
-#pragma unroll
-    for (int k = 0; k < GRAD_PPT; ++k) {
-        const int i = i0 + 64 * k;
-        if (i >= n) break;
+__global__ void __launch_bounds__(256) k_prep_l0(const IN in, int R, int C, float4* __restrict__ tg0,
+                                                 float2* __restrict__ p1, float4* __restrict__ tg1, float min_d,
+                                                 float max_d) {
+    __shared__ typename IN::cell s0[L0_SR][L0_SC];   // as loaded (the packed image: 4 B), IN::val() on every read
+    __shared__ float sh[L0_HR][L0_1C];
+    __shared__ float2 s1[L0_1R][L0_1C];
+    const int tiles_x = (C + L0_TC - 1) / L0_TC;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = ty * L0_TR, x0 = tx * L0_TC;
+    // unconditional loads (every cell maps into the image), four in flight per thread
+#pragma unroll 4
+    for (int k = threadIdx.x; k < L0_SR * L0_SC; k += 256) {
+        const int r = k / L0_SC, c = k - r * L0_SC;
+        const int gy = clampi(refl101(y0 - L0_HALO + r, R), R), gx = clampi(refl101(x0 - L0_HALO + c, C), C);
+        s0[r][c] = in.raw((long)gy * C + gx);
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < L0_TR * L0_TC; k += 256) {
+        const int r = k / L0_TC, c = k - r * L0_TC;
+        const int gy = y0 + r, gx = x0 + c;
+        if (gy >= R || gx >= C) continue;
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        const int m = ws > 0 ? c % ws : 1;   // seam columns as k_gradient (alignFrames360 :4538-4549)
-        const bool seam = ws > 0 && (c >= ws - 1) && (c < 7 * ws + 1) && (m == 0 || m == ws - 1);
-        if (!seam && r >= 1 && r < R - 1 && c >= 1 && c < C - 1) {
-            const float2 f = p0.gd(i), fl = p0.gd(i - 1), fr = p0.gd(i + 1), fu = p0.gd(i - C), fd = p0.gd(i + C);
-            o.x = harm(fl.x, f.x, fr.x);
-            o.y = harm(fu.x, f.x, fd.x);
-            o.z = harm(fl.y, f.y, fr.y);
-            o.w = harm(fu.y, f.y, fd.y);
+        if (grad_live(gy, gx, R, C)) {
+            const int lr = r + L0_HALO, lc = c + L0_HALO;
+            o = grad_of(IN::val(s0[lr][lc]), IN::val(s0[lr][lc - 1]), IN::val(s0[lr][lc + 1]), IN::val(s0[lr - 1][lc]),
+                        IN::val(s0[lr + 1][lc]));
         }
-        tg[i] = o;
-        c += 64;   // the lane's next pixel (C may be below 64 on the small levels: several rows on)
-        while (c >= C) { c -= C; ++r; }
+        tg0[(long)gy * C + gx] = o;
+    }
+    if (!p1) return;   // a one-level pyramid
+    // level-1 pixel (Y0 - 1 + i, X0 - 1 + j): its source rows are the cells 2 i .. 2 i + 4, its source columns the
+    // cells 2 j .. 2 j + 4
+    const int dr = R / 2, dc = C / 2, Y0 = y0 / 2, X0 = x0 / 2;
+    for (int k = threadIdx.x; k < L0_HR * L0_1C; k += 256) {
+        const int s = k / L0_1C, j = k - s * L0_1C;
+        const typename IN::cell* row = s0[s] + 2 * j;
+        const float a = IN::val(row[0]).x, b = IN::val(row[1]).x, c = IN::val(row[2]).x, d = IN::val(row[3]).x,
+                    e = IN::val(row[4]).x;
+        sh[s][j] = c * 6 + (b + d) * 4 + a + e;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < L0_1R * L0_1C; k += 256) {
+        const int i = k / L0_1C, j = k - i * L0_1C;
+        const int ly = Y0 - 1 + i, lx = X0 - 1 + j;
+        if (ly < 0 || ly >= dr || lx < 0 || lx >= dc) continue;
+        const float gray = pyr_gray(sh[2 * i][j], sh[2 * i + 1][j], sh[2 * i + 2][j], sh[2 * i + 3][j], sh[2 * i + 4][j]);
+        const typename IN::cell* r0 = s0[2 * i + 2] + 2 * j + 2;   // level-0 pixel (2 ly, 2 lx)
+        const typename IN::cell* r1 = s0[2 * i + 3] + 2 * j + 2;
+        const float2 v = make_float2(gray, pyr_depth(IN::val(r0[0]).y, IN::val(r0[1]).y, IN::val(r1[0]).y,
+                                                     IN::val(r1[1]).y, min_d, max_d));
+        s1[i][j] = v;
+        if (i >= 1 && i <= L0_TR / 2 && j >= 1 && j <= L0_TC / 2) p1[(long)ly * dc + lx] = v;
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < (L0_TR / 2) * (L0_TC / 2); k += 256) {
+        const int i = k / (L0_TC / 2), j = k - i * (L0_TC / 2);
+        const int ly = Y0 + i, lx = X0 + j;
+        if (ly >= dr || lx >= dc) continue;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (grad_live(ly, lx, dr, dc))   // an interior pixel: its four neighbours are level-1 pixels, all in s1
+            o = grad_of(s1[i + 1][j + 1], s1[i + 1][j], s1[i + 1][j + 2], s1[i][j + 1], s1[i + 2][j + 1]);
+        tg1[(long)ly * dc + lx] = o;
     }
 }
 
-__global__ void k_gradient_levels(GradLevels G) {
-    int l = 0;
-    while (l + 1 < G.nl && (int)blockIdx.x >= G.blk0[l + 1]) ++l;
-    const int R = G.rows[l], C = G.cols[l];
-    const int i0 = (int)((blockIdx.x - G.blk0[l]) * blockDim.x * GRAD_PPT + (threadIdx.x & ~63u) * GRAD_PPT +
-                         (threadIdx.x & 63u));
-    if (i0 >= R * C) return;
-    if (l == 0 && G.pk0) gradient_run(LvPk{G.pk0}, i0, R, C, G.tg[0]);
-    else gradient_run(LvF2{G.p0[l]}, i0, R, C, G.tg[l]);
+// Launch 2, the tail: up to three levels a, b, c below a base level (level 1, or the last level of the previous tail
+// launch) and their gradients.  One workgroup per TL_R x TL_C tile of level a = TL_R/2 x TL_C/2 of b = TL_R/4 x
+// TL_C/4 of c.  It keeps in LDS, per level, the region the next level and the gradients need, pixel (oy + i, ox + j)
+// in cell (i, j) with pixels outside the image left unset and never read:
+//   c: its tile and a ring of 1 (the gradients' neighbours)   6 x 10
+//   b: the pixels under c's region, 2 before and 2 after       15 x 23
+//   a: the pixels under b's region                             33 x 49, from 69 x 101 base pixels read from global
+// Taps go through refl101 on the source level's own coordinates as in k_pyramid; a reflected coordinate lies inside
+// the region, which reaches 2 past the image at most where it needs a tap from there.
+// LDS: 69 x 49 x 4 (row sums, reused by each level) + (33 x 49 + 15 x 23 + 6 x 10) x 8 = 29.2 KB static.
+constexpr int TL_R = 16, TL_C = 32;
+constexpr int TL_T = 512;   // threads: 3381 row sums from global per workgroup, 7 per thread
+constexpr int TL_CR = TL_R / 4 + 2, TL_CC = TL_C / 4 + 2;
+constexpr int TL_BR = 2 * TL_CR + 3, TL_BC = 2 * TL_CC + 3;
+constexpr int TL_AR = 2 * TL_BR + 3, TL_AC = 2 * TL_BC + 3;
+
+struct TailLevels {
+    float2* p0[3];
+    float4* tg[3];
+    int nb;   // levels to build, 1..3
+};
+
+struct SrcGlobal {
+    const float2* p; int C;
+    __device__ __forceinline__ float2 at(int y, int x) const { return p[(long)y * C + x]; }
+};
+template <int NC>
+struct SrcLds {
+    const float2 (*s)[NC]; int oy, ox;
+    __device__ __forceinline__ float2 at(int y, int x) const { return s[y - oy][x - ox]; }
+};
+
+// the DR x DC region of a level at (doy, dox) from its source level (Rs x Cs) into dst, with the pixels of the
+// workgroup's own tr x tc tile at (ty0, tx0) stored to gout; h: (2 DR + 3) x DC row sums
+// CLAMP (the step that reads global memory): pixels outside the image are read at the nearest pixel inside it and
+// their results dropped or left unread, so that the loads stand outside every branch and several iterations' loads
+// are in flight at once; the workgroup's time is the latency of these loads, not their bytes
+template <int DR, int DC, bool CLAMP, class SRC>
+__device__ __forceinline__ void tail_step(const SRC src, int Rs, int Cs, int doy, int dox, float* __restrict__ h,
+                                          float2 (*dst)[DC], float2* __restrict__ gout, int ty0, int tx0, int tr, int tc,
+                                          float min_d, float max_d) {
+    const int Rd = Rs / 2, Cd = Cs / 2, sy0 = 2 * doy - 2;
+#pragma unroll 2
+    for (int k = threadIdx.x; k < (2 * DR + 3) * DC; k += TL_T) {
+        const int s = k / DC, j = k - s * DC;
+        int sy = sy0 + s, xd = dox + j;
+        if (CLAMP) { sy = clampi(sy, Rs); xd = clampi(xd, Cd); }
+        else if (sy < 0 || sy >= Rs || xd < 0 || xd >= Cd) continue;
+        const int sx = 2 * xd;
+        const float a = src.at(sy, refl101(sx - 2, Cs)).x, b = src.at(sy, refl101(sx - 1, Cs)).x, c = src.at(sy, sx).x,
+                    d = src.at(sy, refl101(sx + 1, Cs)).x, e = src.at(sy, refl101(sx + 2, Cs)).x;
+        h[k] = c * 6 + (b + d) * 4 + a + e;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int k = threadIdx.x; k < DR * DC; k += TL_T) {
+        const int i = k / DC, j = k - i * DC;
+        const int yd = doy + i, xd = dox + j;
+        const bool in = yd >= 0 && yd < Rd && xd >= 0 && xd < Cd;
+        if (!CLAMP && !in) continue;
+        const int yq = CLAMP ? clampi(yd, Rd) : yd, xq = CLAMP ? clampi(xd, Cd) : xd;
+        const float2 z0 = src.at(2 * yq, 2 * xq), z1 = src.at(2 * yq, 2 * xq + 1), z2 = src.at(2 * yq + 1, 2 * xq),
+                     z3 = src.at(2 * yq + 1, 2 * xq + 1);
+        if (CLAMP && !in) continue;
+        float hh[5];
+#pragma unroll
+        for (int t = 0; t < 5; ++t) hh[t] = h[(refl101(2 * yd - 2 + t, Rs) - sy0) * DC + j];
+        const float2 v = make_float2(pyr_gray(hh[0], hh[1], hh[2], hh[3], hh[4]),
+                                     pyr_depth(z0.y, z1.y, z2.y, z3.y, min_d, max_d));
+        dst[i][j] = v;
+        if (yd >= ty0 && yd < ty0 + tr && xd >= tx0 && xd < tx0 + tc) gout[(long)yd * Cd + xd] = v;
+    }
+    __syncthreads();
+}
+
+// the gradients of the workgroup's TR x TC tile at (ty0, tx0) of an R x C level held in s (pixel (oy + i, ox + j))
+template <int TR, int TC, int NC>
+__device__ __forceinline__ void tail_grad(const float2 (*s)[NC], int oy, int ox, int R, int C, int ty0, int tx0,
+                                          float4* __restrict__ tg) {
+    for (int k = threadIdx.x; k < TR * TC; k += TL_T) {
+        const int i = k / TC, j = k - i * TC;
+        const int y = ty0 + i, x = tx0 + j;
+        if (y >= R || x >= C) continue;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (grad_live(y, x, R, C)) {
+            const int ly = y - oy, lx = x - ox;
+            o = grad_of(s[ly][lx], s[ly][lx - 1], s[ly][lx + 1], s[ly - 1][lx], s[ly + 1][lx]);
+        }
+        tg[(long)y * C + x] = o;
+    }
+}
+
+__global__ void __launch_bounds__(TL_T) k_prep_tail(const float2* __restrict__ base, int R0, int C0, TailLevels T,
+                                                   float min_d, float max_d) {
+    __shared__ float sh[(2 * TL_AR + 3) * TL_AC];
+    __shared__ float2 sa[TL_AR][TL_AC];
+    __shared__ float2 sb[TL_BR][TL_BC];
+    __shared__ float2 sc[TL_CR][TL_CC];
+    const int Ra = R0 / 2, Ca = C0 / 2;
+    const int tiles_x = (Ca + TL_C - 1) / TL_C;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int Yc = ty * (TL_R / 4), Xc = tx * (TL_C / 4);
+    const int cy = Yc - 1, cx = Xc - 1;             // the regions' first pixels
+    const int by = 2 * cy - 2, bx = 2 * cx - 2;
+    const int ay = 2 * by - 2, ax = 2 * bx - 2;
+    tail_step<TL_AR, TL_AC, true>(SrcGlobal{base, C0}, R0, C0, ay, ax, sh, sa, T.p0[0], 4 * Yc, 4 * Xc, TL_R, TL_C, min_d,
+                            max_d);
+    tail_grad<TL_R, TL_C>(sa, ay, ax, Ra, Ca, 4 * Yc, 4 * Xc, T.tg[0]);
+    if (T.nb < 2) return;
+    const int Rb = Ra / 2, Cb = Ca / 2;
+    tail_step<TL_BR, TL_BC, false>(SrcLds<TL_AC>{sa, ay, ax}, Ra, Ca, by, bx, sh, sb, T.p0[1], 2 * Yc, 2 * Xc, TL_R / 2,
+                            TL_C / 2, min_d, max_d);
+    tail_grad<TL_R / 2, TL_C / 2>(sb, by, bx, Rb, Cb, 2 * Yc, 2 * Xc, T.tg[1]);
+    if (T.nb < 3) return;
+    tail_step<TL_CR, TL_CC, false>(SrcLds<TL_BC>{sb, by, bx}, Rb, Cb, cy, cx, sh, sc, T.p0[2], Yc, Xc, TL_R / 4, TL_C / 4,
+                            min_d, max_d);
+    tail_grad<TL_R / 4, TL_C / 4>(sc, cy, cx, Rb / 2, Cb / 2, Yc, Xc, T.tg[2]);
 }
 
 // setSourceFrame / setTargetFrame level 0 of each sensor's raw images (:480-516): CV_RGB2GRAY on the
@@ -468,19 +663,49 @@ int launch_undistort(r360_frame* f) {
     return 0;
 }
 
-int launch_stitch(r360_frame* f) {
+// experiment builds: R360_STITCH=4 forces the row-major k_stitch4
+static int stitch_form() {
+    static const int form = R360_KNOB("R360_STITCH", 0);
+    return form;
+}
+
+// A frame that only enters batched alignments (compact_all unset: the sequence runner's queued ring, or
+// r360_frame_set_compaction(f, 0)) is lean when its level 0 is streamed as the packed image (the condition under which
+// launch_pyramid skips level 0's compaction) and its stitch is the tiled one: the batched level-0 pass (PF 6), level
+// 1 and the level-0 gradients read pk only, so its build leaves d_sph_bgr, d_sph_depth and lv[0].p0 unwritten
+// (13 of the stitch's 17 bytes per pixel) until a reader asks for them (frame_level0_materialise).
+// R360_LEAN=0 (experiment builds) builds every frame in full.
+bool frame_level0_lean(const r360_frame* f) {
+    static const int pf_env = R360_KNOB("R360_ICP_PF", -1);
+    static const bool pyr_f2 = R360_KNOB("R360_PYR_F2", 0) != 0;   // level 1 from lv[0].p0
+    static const bool lean_on = R360_KNOB("R360_LEAN", 1) != 0;
+    return lean_on && !f->compact_all && !(pf_env == 4 || pf_env == 5) && !pyr_f2 && f->rows > 0 && f->lv[0].pk &&
+           f->lv[0].cols % 64 == 0 && stitch_form() != 4;
+}
+
+int launch_stitch(r360_frame* f, bool lean) {
     const r360_calib* c = f->calib;
     const long n = (long)f->sph_rows * f->sph_cols;
     if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipStreamWaitEvent(f->ctx->stream, e, 0));   // a split upload's BGR copy
     const int slot = timing_begin(f->ctx, "k_stitch");
-    // experiment builds: R360_STITCH=4 forces the row-major k_stitch4
-    static const int form = R360_KNOB("R360_STITCH", 0);
-    if (f->sph_cols % STT_C == 0 && form != 4)
-        hipLaunchKernelGGL(k_stitch_t, dim3((f->sph_cols / STT_C) * ((f->sph_rows + STT_R - 1) / STT_R)), dim3(256), 0,
-                           f->ctx->stream, f->d_bgr, f->d_depth, f->rows, f->cols, f->sph_rows, f->sph_cols,
-                           c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth, c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4],
-                           c->K[6], c->K[7], f->d_sph_bgr, f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
-    else if (f->sph_cols % 4 == 0)
+    const int form = stitch_form();
+    if (lean && !(f->sph_cols % STT_C == 0 && form != 4)) {
+        r360_set_error("lean stitch: the tiled form only");
+        return -1;
+    }
+    if (f->sph_cols % STT_C == 0 && form != 4) {
+        const dim3 grid((f->sph_cols / STT_C) * ((f->sph_rows + STT_R - 1) / STT_R));
+        if (lean)
+            hipLaunchKernelGGL(k_stitch_t<true>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
+                               f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
+                               c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
+                               f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
+        else
+            hipLaunchKernelGGL(k_stitch_t<false>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
+                               f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
+                               c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
+                               f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
+    } else if (f->sph_cols % 4 == 0)
         hipLaunchKernelGGL(k_stitch4, dim3(grid_for(n / 4)), dim3(TPB), 0, f->ctx->stream, f->d_bgr, f->d_depth,
                            f->rows, f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                            c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
@@ -618,28 +843,29 @@ int launch_pyramid(r360_frame* f) {
         return -1;
     }
     static const bool pyr_f2 = R360_KNOB("R360_PYR_F2", 0) != 0;   // experiment builds: level 0 read as float2
-    for (int l = 1; l < f->n_levels; ++l) {
-        const long n = (long)f->lv[l].rows * f->lv[l].cols;
-        // level 1 from level 0's packed image (half the bytes of its float2 image, the same values)
-        if (l == 1 && f->lv[0].pk && !pyr_f2)
-            hipLaunchKernelGGL(k_pyramid<LvPk>, dim3(grid_for(n)), dim3(TPB), 0, f->ctx->stream, LvPk{f->lv[0].pk},
-                               f->lv[0].rows, f->lv[0].cols, f->lv[1].p0, min_d, max_d, 1);
-        else
-            hipLaunchKernelGGL(k_pyramid<LvF2>, dim3(grid_for(n)), dim3(TPB), 0, f->ctx->stream, LvF2{f->lv[l - 1].p0},
-                               f->lv[l - 1].rows, f->lv[l - 1].cols, f->lv[l].p0, min_d, max_d, 1);
-    }
+    // launch 1: level 0's gradients, level 1 and its gradients, from level 0's packed image (half the bytes of its
+    // float2 image, the same values) where the frame has one
     {
-        GradLevels GL{};
-        GL.nl = f->n_levels;
-        GL.pk0 = pyr_f2 ? nullptr : f->lv[0].pk;
-        for (int l = 0; l < f->n_levels; ++l) {
-            GL.p0[l] = f->lv[l].p0;
-            GL.tg[l] = f->lv[l].tg;
-            GL.rows[l] = f->lv[l].rows;
-            GL.cols[l] = f->lv[l].cols;
-            GL.blk0[l + 1] = GL.blk0[l] + (int)(((long)f->lv[l].rows * f->lv[l].cols + TPB * GRAD_PPT - 1) / (TPB * GRAD_PPT));
-        }
-        hipLaunchKernelGGL(k_gradient_levels, dim3(GL.blk0[f->n_levels]), dim3(TPB), 0, f->ctx->stream, GL);
+        const LevelBufs& L0 = f->lv[0];
+        const bool more = f->n_levels > 1;
+        float2* p1 = more ? f->lv[1].p0 : nullptr;
+        float4* tg1 = more ? f->lv[1].tg : nullptr;
+        const dim3 grid(((L0.rows + L0_TR - 1) / L0_TR) * ((L0.cols + L0_TC - 1) / L0_TC));
+        if (L0.pk && !pyr_f2)
+            hipLaunchKernelGGL(k_prep_l0<LvPk>, grid, dim3(256), 0, f->ctx->stream, LvPk{L0.pk}, L0.rows, L0.cols, L0.tg,
+                               p1, tg1, min_d, max_d);
+        else
+            hipLaunchKernelGGL(k_prep_l0<LvF2>, grid, dim3(256), 0, f->ctx->stream, LvF2{L0.p0}, L0.rows, L0.cols, L0.tg,
+                               p1, tg1, min_d, max_d);
+    }
+    // launch 2: the levels below level 1 and their gradients, three per launch
+    for (int l = 1; l + 1 < f->n_levels; l += 3) {
+        TailLevels T{};
+        T.nb = f->n_levels - 1 - l < 3 ? f->n_levels - 1 - l : 3;
+        for (int k = 0; k < T.nb; ++k) { T.p0[k] = f->lv[l + 1 + k].p0; T.tg[k] = f->lv[l + 1 + k].tg; }
+        const LevelBufs& A = f->lv[l + 1];
+        hipLaunchKernelGGL(k_prep_tail, dim3(((A.rows + TL_R - 1) / TL_R) * ((A.cols + TL_C - 1) / TL_C)), dim3(TL_T), 0,
+                           f->ctx->stream, f->lv[l].p0, f->lv[l].rows, f->lv[l].cols, T, min_d, max_d);
     }
     // the compacted points feed a lone alignment's passes (PF 5); batched passes stream the images (PF 6 at level 0
     // where its rows split into whole waves, PF 8 on levels of >= 64 columns), so frames that only enter batches
@@ -665,6 +891,7 @@ int launch_src_compaction(r360_frame* f, unsigned levels) {
     for (int l = 0; l < f->n_levels; ++l)
         if ((levels >> l) & 1u) l1 = l + 1;
     if (l1 == 0) return 0;
+    if ((levels & 1u) && frame_level0_materialise(f)) return -1;   // level 0's points come from lv[0].p0
     SrcGrid G{};
     G.nl = l1;
     for (int l = 0; l < l1; ++l)

@@ -2509,6 +2509,10 @@ static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int
     return {pf, nb};
 }
 
+int icp_pass_form(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched) {
+    return pass_grid(ctx, src->lv[level], occ, 1, batched, !batched && ((src->compacted >> level) & 1u)).pf;
+}
+
 // deferred-queue entries one job's PF 3 / PF 4 pass needs: per wave ceil(npx / stride) * 64
 static long defer_need(int npx, int nb) {
     const long stride = (long)nb * TPB;

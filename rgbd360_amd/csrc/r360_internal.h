@@ -546,7 +546,9 @@ struct r360_frame {
     unsigned compacted = 0;            // bit l: lv[l].pts / d_npts[l] hold level l's compacted source points
     // the pyramid build compacts every level: a lone alignment's passes (PF 5) read the compacted points.  Frames that
     // only enter batched alignments (compact_all unset: the sequence runner's queued ring) skip it on every level a
-    // batched pass streams as an image (PF 6 at level 0, PF 8 above; round 6: two launches per frame fewer)
+    // batched pass streams as an image (PF 6 at level 0, PF 8 above; round 6: two launches per frame fewer), and
+    // where level 0 is streamed packed their stitch writes lv[0].pk only (frame_level0_lean; `built` then lacks
+    // R360_BUILT_LEVEL0 until frame_level0_materialise)
     bool compact_all = true;
     SphereCloudHost* sphere_cloud = nullptr;  // sphereCloud set by loadCloud (Frame360.h:187-193)
     // builds recorded on the frame's build event (runtime.cpp frame_build_event_record): a dense-queue job snapshots
@@ -558,7 +560,16 @@ struct r360_frame {
 // ------------------------------------------------------------------ kernel launchers
 hipStream_t capture_stream(r360_ctx* ctx);   // ctx->cap_stream, created on first use (nullptr on failure)
 int launch_undistort(r360_frame* f);
-int launch_stitch(r360_frame* f);
+// lean: only lv[0].pk is stored (frame_level0_lean: the frame's other level-0 outputs have no reader yet)
+int launch_stitch(r360_frame* f, bool lean = false);
+bool frame_level0_lean(const r360_frame* f);
+// The full level-0 outputs (d_sph_bgr, d_sph_depth, lv[0].p0) of a frame whose last build was lean: the full stitch
+// again on the frame's stream, from the raw images still resident (an upload clears `built`), waited for, and
+// R360_BUILT_LEVEL0 set.  Every reader of those buffers other than the packed level-0 pass calls it first; a no-op
+// for a frame that has them.
+int frame_level0_materialise(r360_frame* f);
+// the form (PF) of a plain or occlusion pass over level `level` of src (icp_kernels.hip pass_grid)
+int icp_pass_form(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched);
 int launch_pyramid(r360_frame* f);
 int launch_src_compaction(r360_frame* f, unsigned levels);   // compacted source points of the levels (bit l)
 constexpr int R360_CU_MASK_WORDS = 8;
