@@ -595,6 +595,17 @@ int r360_rank6(const float* M, int n, int* ranks);
 /* The device GN solve x = -H^-1 g (RegisterPhotoICP.h:4693; Gaussian elimination with partial pivoting in
  * double) of n systems: H row-major n x 36, g n x 6, x n x 6. */
 int r360_solve6(const double* H, const double* g, int n, double* x);
+/* What the pass launcher picks for level `level` of src_frame (host only, nothing is launched): the pass form
+ * (PF) and the workgroups per job, for a lone pass (batched = 0; occlusion 0 / 1 / 2) or a batched launch
+ * (batched = 1; occlusion 0 only). */
+int r360_icp_pass_grid(r360_ctx* ctx, const r360_frame* src_frame, int level, int occlusion, int batched, int* pf,
+                       int* nb);
+/* r360_icp_eval on the batched grid: one eval-only pass of n <= R360_MAX_BATCH_ALIGN jobs at `level`, the jobs
+ * prepared and launched as r360_align360_batch_async prepares and launches its passes.  poses: n col-major 4x4;
+ * every output holds n entries (H n x 36, g n x 6), job j's raw pass sums.  Refused while a batch is pending. */
+int r360_icp_eval_batch(r360_ctx* ctx, int n, r360_frame* const* trg, r360_frame* const* src, int level,
+                        const float* poses, int method, const r360_icp_params* p, double* H, double* g,
+                        double* err2, int* n_valid, int* n_visible);
 int r360_libm_eval(const float* x, const float* y, const float* z, int n, float* asin_out, float* atan2_out,
                    int on_device);
 

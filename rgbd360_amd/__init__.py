@@ -223,6 +223,9 @@ _SIGS = [
                                 _IP]),
     ("r360_icp_eval_occ", C.c_int, [_P, _P, _P, C.c_int, _FP, C.c_int, C.c_int, C.POINTER(IcpParams), _DP, _DP,
                                     _DP, _IP, _IP]),
+    ("r360_icp_pass_grid", C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _IP, _IP]),
+    ("r360_icp_eval_batch", C.c_int, [_P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _FP, C.c_int,
+                                      C.POINTER(IcpParams), _DP, _DP, _DP, _IP, _IP]),
     ("r360_exp_se3", None, [_DP, C.c_int, _FP]),
     ("r360_align_pinhole", C.c_int, [_P, _P, _P, C.c_int, _FP, C.c_int, _FP, C.POINTER(IcpParams), _FP, _FP, _FP,
                                      C.POINTER(IcpStats)]),
@@ -1014,6 +1017,24 @@ def align360_batch(ctx: "Context", pairs, inits=None, method: int = PHOTO_CONSIS
     return poses, H, go.reshape(n, 6).copy(), list(st), ill
 
 
+def align_eval_batch(ctx: "Context", pairs, level: int, poses, method: int = PHOTO_DEPTH, params: "IcpParams" = None):
+    """RegisterPhotoICP.eval on the batched grid (r360_icp_eval_batch, a test hook): one eval-only pass of
+    pairs = [(target Frame360, source Frame360), ...] at `level`, job j at poses[j].  Returns (H [n,6,6], g [n,6],
+    err2 [n], n_valid [n], n_visible [n])."""
+    n = len(pairs)
+    p = params or IcpParams.default()
+    trg = (C.c_void_p * n)(*[t.h for t, _ in pairs])
+    src = (C.c_void_p * n)(*[s.h for _, s in pairs])
+    assert len(poses) == n
+    ps = np.ascontiguousarray(np.concatenate([_mat16(P) for P in poses]), np.float32)
+    H, g, e2 = np.zeros(36 * n), np.zeros(6 * n), np.zeros(n)
+    nv, nvis = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    _check(lib().r360_icp_eval_batch(ctx.h, n, trg, src, level, _fptr(ps), method, C.byref(p), H.ctypes.data_as(_DP),
+                                     g.ctypes.data_as(_DP), e2.ctypes.data_as(_DP), nv.ctypes.data_as(_IP),
+                                     nvis.ctypes.data_as(_IP)), "r360_icp_eval_batch")
+    return H.reshape(n, 6, 6), g.reshape(n, 6), e2, nv, nvis
+
+
 class DenseQueue:
     """The alignFrames360 stage of many concurrent registrations batched on one stream (r360_dense_queue):
     submit from any thread, collect by ticket; a job's result equals the single-pair alignment."""
@@ -1213,6 +1234,14 @@ class RegisterPhotoICP:
                                    C.byref(self.params), H.ctypes.data_as(_DP), g.ctypes.data_as(_DP),
                                    C.byref(e2), C.byref(nv), C.byref(nvis)), "icp_eval")
         return H.reshape(6, 6), g, e2.value, nv.value, nvis.value
+
+    def pass_grid(self, level: int, occlusion: int = 0, batched: bool = False):
+        """(pass form PF, workgroups per job) the launcher picks for `level` of the source frame (r360_icp_pass_grid,
+        a test hook; host only)."""
+        pf, nb = C.c_int(), C.c_int()
+        _check(lib().r360_icp_pass_grid(self.ctx.h, self.src.h, level, occlusion, int(bool(batched)), C.byref(pf),
+                                        C.byref(nb)), "icp_pass_grid")
+        return pf.value, nb.value
 
     def eval_occ(self, level: int, pose, method: int = PHOTO_DEPTH, occlusion: int = 1):
         """One occlusion-aware pass at a fixed pose: H, g of calcHessGrad_sphereOcc{occlusion}, the value

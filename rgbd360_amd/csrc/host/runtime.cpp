@@ -1377,6 +1377,75 @@ extern "C" int r360_icp_eval_occ(r360_ctx* ctx, r360_frame* trg, r360_frame* src
     return 0;
 }
 
+// Test hook: the form and the workgroups per job that pass_grid picks for a level of src (nothing is launched)
+extern "C" int r360_icp_pass_grid(r360_ctx* ctx, const r360_frame* src, int level, int occlusion, int batched, int* pf,
+                                  int* nb) {
+    CHECK_ARG(ctx && src, "null arg");
+    if (bind_device(ctx->device)) return -1;
+    CHECK_ARG(src->built & R360_BUILD_PYRAMID, "the frame needs R360_BUILD_PYRAMID (its built levels decide the form)");
+    CHECK_ARG(level >= 0 && level < src->n_levels, "level out of range");
+    CHECK_ARG(occlusion >= 0 && occlusion <= 2, "occlusion must be 0, 1 or 2");
+    CHECK_ARG(!(batched && occlusion), "batched passes: occlusion variants run one alignment per launch");
+    icp_pass_grid(ctx, src, level, occlusion, batched != 0, pf, nb);
+    return 0;
+}
+
+// Test hook: one eval-only pass of n jobs on the batched grid, prepared as align360_batch_enqueue prepares its passes
+// and launched as icp_eval_sums launches the lone one; job j's raw sums
+extern "C" int r360_icp_eval_batch(r360_ctx* ctx, int n, r360_frame* const* trg, r360_frame* const* src, int level,
+                                   const float* poses, int method, const r360_icp_params* p, double* H, double* g,
+                                   double* err2, int* n_valid, int* n_visible) {
+    if (ctx && bind_device(ctx->device)) return -1;
+    CHECK_ARG(ctx && trg && src && poses && p && H && g, "null arg");
+    CHECK_ARG(n >= 1 && n <= R360_MAX_BATCH, "batch size must be 1..R360_MAX_BATCH");
+    CHECK_ARG(!ctx->batch_pending, "a batch is pending on this ctx (r360_align360_batch_result)");
+    CHECK_ARG(method >= 0 && method <= 2, "invalid method");
+    for (int j = 0; j < n; ++j) {
+        if (int rc = check_pair(ctx, trg[j], src[j], p)) return rc;
+        CHECK_ARG(src[j]->sph_rows == src[0]->sph_rows && src[j]->sph_cols == src[0]->sph_cols,
+                  "batched alignments need frames of one sphere size");
+        CHECK_ARG(level >= 0 && level < src[j]->n_levels && level < trg[j]->n_levels, "level out of range");
+    }
+    for (int j = 0; j < n; ++j)
+        if (pair_level0_ready(ctx, trg[j], src[j], 0, true)) return -1;
+    if (ensure_batch(ctx, n, (long)src[0]->lv[0].rows * src[0]->lv[0].cols)) return -1;
+    std::vector<r360_frame*> fr;
+    for (int j = 0; j < n; ++j) { fr.push_back(trg[j]); fr.push_back(src[j]); }
+    if (ctx_wait_frames(ctx, fr.data(), 2 * n)) return -1;
+    for (int j = 0; j < n; ++j) {
+        IcpState* h = ctx->h_bstate + j;
+        memset(h, 0, sizeof(IcpState));
+        memcpy(h->pose, poses + 16 * j, sizeof(float) * 16);
+        memcpy(h->cand, poses + 16 * j, sizeof(float) * 16);
+        h->dbg[8] = ~0ull;
+    }
+    R360_HIP(hipMemcpyAsync(ctx->d_bstate, ctx->h_bstate, sizeof(IcpState) * n, hipMemcpyHostToDevice, ctx->stream));
+    const size_t tk = (size_t)R360_TICKET_GROUPS * R360_TICKET_STRIDE;
+    IcpJobs jobs;
+    for (int j = 0; j < n; ++j) {
+        IcpJob& J = jobs.j[j];
+        J.src = src[j]->lv[level].p0; J.trg = trg[j]->lv[level].p0; J.tg = trg[j]->lv[level].tg;
+        J.pts = src[j]->lv[level].pts; J.npts = src[j]->d_npts + level;
+        J.spk = src[j]->lv[level].pk; J.tpk = trg[j]->lv[level].pk;
+        J.S = ctx->d_bstate + j;
+        J.partials = ctx->d_bpartials + (size_t)j * 32 * ctx->partials_cap;
+        J.gcnt = ctx->d_bgticket + (size_t)j * tk;
+        J.dq = ctx->d_bdefer + (size_t)j * ctx->bdefer_cap;
+    }
+    const IcpConst C = make_const(p, level, src[0]->lv[level].rows * src[0]->lv[level].cols, 0);
+    if (int rc = launch_icp_jobs(ctx, jobs, n, src[0], level, method, C, 0, 1)) return rc;
+    R360_HIP(hipMemcpyAsync(ctx->h_bstate, ctx->d_bstate, sizeof(IcpState) * n, hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx_wait(ctx)) return -1;
+    for (int j = 0; j < n; ++j) {
+        const double* s = ctx->h_bstate[j].sums;
+        sums_hg(s, H + 36 * j, g + 6 * j);
+        if (err2) err2[j] = s[R360_SUM_ERR2];
+        if (n_valid) n_valid[j] = (int)s[R360_SUM_NVALID];
+        if (n_visible) n_visible[j] = (int)s[R360_SUM_NVIS];
+    }
+    return 0;
+}
+
 // CPose3D::exp (host copy for callers of the façade, e.g. the Register() alias)
 extern "C" void r360_exp_se3(const double mu[6], int pseudo, float T[16]) {
     const double wx = mu[3], wy = mu[4], wz = mu[5];

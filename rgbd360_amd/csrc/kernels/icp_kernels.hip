@@ -192,9 +192,11 @@ __device__ __forceinline__ Proj project_exact(const Pose12& P, const Lut3& l, fl
 // (correctly rounded sqrt), then hardware rsq, theta + pi in float, atan2 with one reciprocal, and floor(x + 0.5) rounding
 // (= roundf away from the .5 boundaries, which are all inside the guard bands) that shares its
 // floor with the guard test.  A lane inside a guard band, or NaN, is flagged in o.fix.
-// LEAN (PF 5): p' by three fused multiply-adds per coordinate instead of the reference's six rounded
-// operations (|p'| then differs from the reference's by about an ulp; the projection's guard bands are three
-// orders of magnitude wider than that, and deferred lanes are re-projected from the exact p').
+// LEAN (PF 5 from R360_EXACT_BELOW valid points up, PF 6 / 8 / 9): p' by three fused multiply-adds per coordinate
+// instead of the reference's six rounded operations (|p'| then differs from the reference's by about an ulp; the
+// projection's guard bands are three orders of magnitude wider than that, and deferred lanes are re-projected from
+// the exact p').
+constexpr int R360_EXACT_BELOW = 512;   // PF 5: valid source points below which p' and |p'| are the reference's
 template <bool LEAN = false>
 __device__ __forceinline__ Proj project_fast(const Pose12& P, const Lut3& l, float gray_s, int nRows, int nCols,
                                              float angle_res_inv, float asin_out) {
@@ -1002,7 +1004,18 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                                    __uint_as_float(v[3])), base + lane < nv};
         };
         auto prj = [&](const Src& x) {
-            return project_fast<LEAN>(P, Lut3{x.p.x, x.p.y, x.p.z, x.valid}, x.p.w, nRows, nCols, angle_res_inv, asin_out);
+            // Below R360_EXACT_BELOW valid source points (wave-uniform) PF 5 takes the reference's p' and |p'|
+            // (uncontracted transform, correctly rounded root).  The contracted transform moves |p'| by an ulp or two,
+            // and the depth residual T - |p'| magnifies that by |p'| / |T - |p'||: at a residual of 2 % of the range
+            // one pixel's squared term is off by 1.8e-5 of itself.  Over N pixels of equal share the signs average
+            // that to 1.8e-5 / sqrt(N), under the suite's 1e-6 bar on the squared error from N = 330; a level of 11 /
+            // 27 valid points, one of them carrying half the sum, was measured 1.7e-6 / 1.9e-6 off
+            // (tests/test_gpu_icp_shapes.py).  PF 5 is the form of every level below 64 columns, lone or batched; the
+            // image forms (PF 6 / 8 / 9, levels of 64 columns and more) keep the lean transform throughout.
+            const Lut3 l{x.p.x, x.p.y, x.p.z, x.valid};
+            if (LEAN && nv < R360_EXACT_BELOW)
+                return project_fast<false>(P, l, x.p.w, nRows, nCols, angle_res_inv, asin_out);
+            return project_fast<LEAN>(P, l, x.p.w, nRows, nCols, angle_res_inv, asin_out);
         };
         auto defer = [&](Proj& o, int base) {
             const unsigned long long m = __ballot(o.fix);
@@ -2511,6 +2524,12 @@ static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int
 
 int icp_pass_form(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched) {
     return pass_grid(ctx, src->lv[level], occ, 1, batched, !batched && ((src->compacted >> level) & 1u)).pf;
+}
+
+void icp_pass_grid(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched, int* pf, int* nb) {
+    const PassGrid G = pass_grid(ctx, src->lv[level], occ, 1, batched, !batched && ((src->compacted >> level) & 1u));
+    if (pf) *pf = G.pf;
+    if (nb) *nb = G.nb;
 }
 
 // deferred-queue entries one job's PF 3 / PF 4 pass needs: per wave ceil(npx / stride) * 64

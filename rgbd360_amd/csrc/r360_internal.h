@@ -570,6 +570,8 @@ bool frame_level0_lean(const r360_frame* f);
 int frame_level0_materialise(r360_frame* f);
 // the form (PF) of a plain or occlusion pass over level `level` of src (icp_kernels.hip pass_grid)
 int icp_pass_form(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched);
+// the same with the workgroups per job (r360_icp_pass_grid)
+void icp_pass_grid(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched, int* pf, int* nb);
 int launch_pyramid(r360_frame* f);
 int launch_src_compaction(r360_frame* f, unsigned levels);   // compacted source points of the levels (bit l)
 constexpr int R360_CU_MASK_WORDS = 8;

@@ -13,6 +13,7 @@ import pytest
 
 import rgbd360_amd as R
 from oracle import oracle360 as O
+from _cases import icp_check as _icp_check
 
 pytestmark = pytest.mark.gpu
 
@@ -106,18 +107,6 @@ def test_source_points_compaction(qvga):
             ares = 2 * np.pi / cols
             phi = (rows / 2 - 0.5 - r) * ares
             np.testing.assert_allclose(pts[:, 0], d[valid] * np.sin(phi), atol=2e-5)
-
-
-def _icp_check(H, g, e2, nv, nvis, Hr, gr, e2r, nvr, nvisr, npx):
-    """The projection is bit-identical (glibc-exact asinf/atan2f port), so pixel sets and counts
-    match exactly; the sums differ only by summation order (GPU: per-thread f32 partials over a few
-    pixels, then fp64), bounded per component by 1e-5 of the Cauchy-Schwarz scale sqrt(H_kk e2)."""
-    assert (nv, nvis) == (nvr, nvisr)
-    sH = np.abs(Hr).max()
-    assert np.abs(H - Hr).max() <= 1e-5 * sH
-    scale = np.sqrt(np.abs(np.diag(Hr)) * max(e2r, 1e-30))
-    assert (np.abs(g - gr) <= 1e-5 * scale + 1e-12).all(), (g - gr, scale)
-    assert abs(e2 - e2r) <= 1e-6 * e2r
 
 
 @pytest.mark.parametrize("method", [0, 1, 2])

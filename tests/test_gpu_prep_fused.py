@@ -11,6 +11,7 @@ import pytest
 
 import rgbd360_amd as R
 from oracle import oracle360 as O
+from _cases import noise_sphere as sphere_images
 
 pytestmark = pytest.mark.gpu
 
@@ -18,27 +19,6 @@ FIELDS = ("gray", "depth", "gx", "gy", "dgx", "dgy")
 # (sphere rows, sphere columns, pyramid levels the library builds for it)
 SHAPES = [(2, 8, 1), (4, 16, 2), (20, 72, 2), (52, 416, 3), (72, 480, 4), (80, 576, 5), (96, 768, 6), (64, 384, 6),
           (130, 1040, 2)]
-
-
-def sphere_images(rows, cols, seed):
-    """BGR uniform; range uniform in [0, 7000) mm with 20 % zeros; a block of the depth bounds' own values (300, 301,
-    5999, 6000 mm); a flat patch (harm() = 0: no strict monotony) and a ramp (harm()'s harmonic-mean branch)."""
-    rng = np.random.default_rng(seed)
-    bgr = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
-    dep = rng.integers(0, 7000, (rows, cols)).astype(np.uint16)
-    dep[rng.random((rows, cols)) < 0.2] = 0
-    bounds = np.array([300, 301, 5999, 6000], np.uint16)
-    r0, c0 = rows // 2, cols // 2
-    hb, wb = min(4, rows - r0), min(8, cols - c0)
-    dep[r0:r0 + hb, c0:c0 + wb] = np.resize(bounds, (hb, wb))
-    hp, wp = min(12, rows), min(24, cols // 2)
-    bgr[:hp, :wp] = 90                      # flat patch
-    dep[:hp, :wp] = 2000
-    ramp = np.arange(wp, dtype=np.int64)    # monotone ramp, rows shifted so that it rises downwards too
-    rr = ramp[None, :] + np.arange(hp)[:, None]
-    bgr[rows - hp:, cols - wp:] = (40 + 3 * rr)[..., None].astype(np.uint8)
-    dep[rows - hp:, cols - wp:] = (1000 + 25 * rr).astype(np.uint16)
-    return bgr, dep
 
 
 @pytest.fixture(scope="module")
