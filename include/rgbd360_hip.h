@@ -545,6 +545,25 @@ typedef struct {
 int r360_frame_get_cloud(r360_frame* f, float* xyz4, uint8_t* rgb4, float* nrm4, float* dist);
 int r360_frame_get_labels(r360_frame* f, int* lab, int* labf);
 int r360_frame_get_regions(r360_frame* f, int sensor, r360_region* out, int cap, int* n);
+/* Parity hook: the frame's segmentation stage on given fields instead of the ones its depth images give.  xyz4
+ * [8][h][w][4] (h = rows / 2, w = cols / 2; NaN = no point), nrm [8][h][w][nrm_comps] (nrm_comps 3 or 4: unit
+ * normals, NaN = none) and rgb4 [8][h][w][4] {r, g, b, -} go where k_cloud, k_normals and k_rgb write: the points as
+ * {x, y, z, 0}, the normals with their fourth component p.n computed on the device as k_normals computes it (a given
+ * fourth component is ignored), the colours through the centre pixels of the frame's BGR images, which the stage's
+ * k_rgb reads (the frame's uploaded images are overwritten: upload again before an ordinary build).  Then the
+ * ordinary launcher of a build (connected components, plane fits, refinement, statistics, contours, voxel fallback,
+ * hull prefilter, publication) runs on the frame's buffers on its context's stream.  The host assembly does not
+ * run: the frame's PbMap is empty afterwards.  r360_frame_get_labels, r360_frame_get_regions and
+ * r360_frame_get_region_detail show the result.  Returns 0, or < 0 with the capacity error of an ordinary build
+ * ("plane segmentation capacity exceeded (code ...)"); *err_code (optional) receives the stage's error bits. */
+int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const float* nrm, int nrm_comps, const uint8_t* rgb4,
+                            int* err_code);
+/* Region `region` of `sensor` as the segmentation stage left it, before the hull prefilter and the host assembly:
+ * stats[20] = the final inliers' exact moments (PlaneOut::stats: n, s1[3], s2[6] as (low, high) 64-bit words,
+ * c[4]), bounds[6] = local-frame min xyz, max xyz, and the traced contour's points in trace order from the device
+ * pool (contour4 [cap][4], optional; *n_contour = their number, 0 for a region that takes the voxel fallback). */
+int r360_frame_get_region_detail(r360_frame* f, int sensor, int region, int64_t* stats, float* bounds,
+                                 float* contour4, int cap, int* n_contour);
 
 /* ---------------------------------------------------------------- multi-GPU sequence driver (§8(e))
  * Pairs of a sequence shard one contiguous run per GPU (one process per GPU); the per-pair records

@@ -262,6 +262,8 @@ _SIGS = [
     ("r360_frame_get_cloud", C.c_int, [_P, _FP, _P, _FP, _FP]),
     ("r360_frame_get_labels", C.c_int, [_P, _IP, _IP]),
     ("r360_frame_get_regions", C.c_int, [_P, C.c_int, C.POINTER(Region), C.c_int, _IP]),
+    ("r360_frame_segment_eval", C.c_int, [_P, _FP, _FP, C.c_int, _P, _IP]),
+    ("r360_frame_get_region_detail", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), _FP, _FP, C.c_int, _IP]),
     ("r360_comm_unique_id", C.c_int, [_P]),
     ("r360_comm_init", C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
     ("r360_comm_destroy", None, [_P]),
@@ -744,6 +746,46 @@ class Frame360:
         return [dict(label=r.label, count=r.count, start_idx=r.start_idx, n_contour=r.n_contour, n_fit=r.n_fit,
                      centroid=np.array(r.centroid[:]), cov=np.array(r.cov[:]).reshape(3, 3),
                      model=np.array(r.model[:]), curvature=r.curvature) for r in arr[:n.value]]
+
+    def segment_eval(self, xyz4: np.ndarray, nrm: np.ndarray, rgb4: np.ndarray) -> int:
+        """Parity hook (r360_frame_segment_eval): the frame's segmentation stage on given points [8, h, w, 4], unit
+        normals [8, h, w, 3 or 4] and colours [8, h, w, 4] (h = rows / 2, w = cols / 2).  Returns 0; a capacity
+        error raises RuntimeError with the stage's error bits in its `code` attribute.  labels(), regions(k) and
+        region_detail(k, m) show the result; the frame's images are overwritten and its PbMap is empty."""
+        h, w = self.rows // 2, self.cols // 2
+        xyz4 = np.ascontiguousarray(xyz4, np.float32)
+        nrm = np.ascontiguousarray(nrm, np.float32)
+        rgb4 = np.ascontiguousarray(rgb4, np.uint8)
+        if xyz4.shape != (8, h, w, 4) or nrm.shape[:3] != (8, h, w) or nrm.shape[3] not in (3, 4) or \
+                rgb4.shape != (8, h, w, 4):
+            raise ValueError(f"segment_eval: fields of 8 x {h} x {w} expected")
+        code = C.c_int(0)
+        rc = lib().r360_frame_segment_eval(self.h, _fptr(xyz4), _fptr(nrm), nrm.shape[3], _vptr(rgb4), C.byref(code))
+        if rc < 0:
+            e = RuntimeError(f"segment_eval failed ({rc}): {lib().r360_last_error().decode()}")
+            e.code = code.value
+            raise e
+        return rc
+
+    def region_detail(self, sensor: int, region: int) -> dict:
+        """Region `region` of `sensor` before the hull prefilter and the host assembly: the exact moments of its final
+        inliers (Python integers: n, s1[3], s2[6] = xx xy xz yy yz zz, c[4]), its local-frame bounds and its traced
+        contour's points [n_contour, 4] in trace order (none for a region that takes the voxel fallback)."""
+        st = (C.c_int64 * 20)()
+        bounds = np.zeros(6, np.float32)
+        n = C.c_int()
+        _check(lib().r360_frame_get_region_detail(self.h, sensor, region, st, _fptr(bounds), None, 0, C.byref(n)),
+               "get_region_detail")
+        contour = np.zeros((max(n.value, 1), 4), np.float32)
+        if n.value:
+            _check(lib().r360_frame_get_region_detail(self.h, sensor, region, None, None, _fptr(contour), n.value,
+                                                      C.byref(n)), "get_region_detail")
+        s2 = []
+        for k in range(6):
+            v = (int(st[4 + 2 * k]) & 0xFFFFFFFFFFFFFFFF) | ((int(st[5 + 2 * k]) & 0xFFFFFFFFFFFFFFFF) << 64)
+            s2.append(v - (1 << 128) if v >> 127 else v)
+        return dict(n=int(st[0]), s1=[int(st[1 + k]) for k in range(3)], s2=s2, c=[int(st[16 + k]) for k in range(4)],
+                    bmin=bounds[:3].copy(), bmax=bounds[3:].copy(), contour=contour[:n.value].copy())
 
     def sphere(self):
         bgr = np.zeros((self.sph_rows, self.sph_cols, 3), np.uint8)

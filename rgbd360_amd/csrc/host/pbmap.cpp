@@ -1680,6 +1680,105 @@ extern "C" int r360_frame_get_regions(r360_frame* f, int sensor, r360_region* ou
     return 0;
 }
 
+// Parity hook (rgbd360_hip.h): the segmentation stage of a build on given points, normals and colours.  The launcher,
+// buffers, stream and voxel scratch are those planes_enqueue uses for a lone frame (kernel by kernel, no graph); only
+// the stage's inputs come from the caller, and the host assembly is left out (the frame's PbMap is empty).
+extern "C" int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const float* nrm, int nrm_comps,
+                                       const uint8_t* rgb4, int* err_code) {
+    CHECK_ARG(f && xyz4 && nrm && rgb4 && (nrm_comps == 3 || nrm_comps == 4), "segment_eval: bad arguments");
+    if (bind_device(f->ctx->device)) return -1;
+    CHECK_ARG(f->rows > 0, "a sphere-only frame has no sensor images");
+    planes_join(f);   // a previous build's assembly (or a plane queue's batch) still using the buffers
+    if (plane_bufs_alloc(f)) return -1;
+    r360_ctx* ctx = f->ctx;
+    hipStream_t st = ctx->stream;
+    PlaneBufs& P = f->pl;
+    const int w = P.w, h = P.h, rows = f->rows, cols = f->cols;
+    const size_t T = 8 * (size_t)w * h;
+    // the colours as the BGR images' centre pixels (2 r + 1, 2 c + 1), which launch_rgb reads
+    std::vector<uint8_t> bgr((size_t)8 * rows * cols * 3, 0);
+    for (int s = 0; s < 8; ++s)
+        for (int r = 0; r < h; ++r)
+            for (int c = 0; c < w; ++c) {
+                const uint8_t* q = rgb4 + 4 * (((size_t)s * h + r) * w + c);
+                uint8_t* d = bgr.data() + (((size_t)s * rows + 2 * r + 1) * cols + 2 * c + 1) * 3;
+                d[0] = q[2]; d[1] = q[1]; d[2] = q[0];
+            }
+    std::vector<float> n4;
+    if (nrm_comps == 3) {
+        n4.resize(4 * T);
+        for (size_t i = 0; i < T; ++i) {
+            for (int k = 0; k < 3; ++k) n4[4 * i + k] = nrm[3 * i + k];
+            n4[4 * i + 3] = 0.f;
+        }
+    }
+    if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipEventSynchronize(e));   // a split upload's copy in flight
+    R360_HIP(hipStreamSynchronize(st));
+    f->bgr_split = false;
+    R360_HIP(hipMemcpy(f->d_bgr, bgr.data(), bgr.size(), hipMemcpyHostToDevice));
+    R360_HIP(hipMemcpy(P.cloud, xyz4, sizeof(float4) * T, hipMemcpyHostToDevice));
+    R360_HIP(hipMemcpy(P.nrm, nrm_comps == 3 ? n4.data() : nrm, sizeof(float4) * T, hipMemcpyHostToDevice));
+    const PlaneGeom G = plane_geom(f);
+    long cells, entries, groups;
+    vox_scratch_need(G, &cells, &entries, &groups);
+    if (ctx_vhash_reserve(ctx, cells, entries, groups)) return -1;
+    PlaneBatch B;
+    std::memset(&B, 0, sizeof B);
+    B.f[0] = plane_dev(f, VoxScratch{ctx->d_vhash, (unsigned long long)ctx->vhash_cap, ctx->d_vlist, ctx->d_vcnt});
+    P.ticket.reset();
+    delete f->pbmap;
+    f->pbmap = nullptr;
+    f->built = 0;   // the images are not the uploaded ones any more
+    if (launch_segment_inputs(B, 1, G, st)) return -1;
+    if (launch_segmentation(B, 1, G, st, ctx, nullptr)) return -1;
+    if (launch_plane_publish(B, 1, st)) return -1;
+    R360_HIP(hipEventRecord(P.done, st));
+    R360_HIP(hipStreamSynchronize(st));
+    f->built = R360_BUILD_CLOUD | R360_BUILD_PLANES;
+    if (err_code) *err_code = P.h_nmodels[8];
+    if (planes_capacity_ok(f)) {
+        P.worker_rc = -1;
+        P.worker_err = r360_last_error();
+        return -1;
+    }
+    P.worker_rc = 0;
+    P.worker_err.clear();
+    f->pbmap = new PbMapHost;
+    return 0;
+}
+
+extern "C" int r360_frame_get_region_detail(r360_frame* f, int sensor, int region, int64_t* stats, float* bounds,
+                                            float* contour4, int cap, int* n_contour) {
+    if (int rc = ready(f)) return rc;
+    CHECK_ARG(f->pl.cloud, "frame planes were loaded, not built: no per-sensor regions");
+    CHECK_ARG(sensor >= 0 && sensor < 8, "sensor out of range");
+    PlaneBufs& P = f->pl;
+    CHECK_ARG(region >= 0 && region < P.h_nmodels[sensor], "region out of range");
+    const PlaneOut& O = P.h_out[sensor * R360_MAX_MODELS + region];
+    if (stats) {
+        stats[0] = O.stats.n;
+        for (int k = 0; k < 3; ++k) stats[1 + k] = O.stats.s1[k];
+        for (int k = 0; k < 6; ++k) {
+            const unsigned __int128 u = (unsigned __int128)O.stats.s2[k];
+            stats[4 + 2 * k] = (int64_t)(unsigned long long)u;
+            stats[5 + 2 * k] = (int64_t)(unsigned long long)(u >> 64);
+        }
+        for (int k = 0; k < 4; ++k) stats[16 + k] = O.stats.c[k];
+    }
+    if (bounds)
+        for (int k = 0; k < 3; ++k) { bounds[k] = O.bmin[k]; bounds[3 + k] = O.bmax[k]; }
+    const long nc = O.n_contour > 0 ? O.n_contour : 0;
+    if (n_contour) *n_contour = (int)nc;
+    if (contour4 && nc > 0) {
+        CHECK_ARG(cap >= nc, "region contour: buffer too small");
+        CHECK_ARG(O.contour_off >= 0 && O.contour_off + nc <= P.contour_cap, "region contour outside the pool");
+        if (bind_device(f->ctx->device)) return -1;
+        R360_HIP(hipStreamSynchronize(f->ctx->stream));
+        R360_HIP(hipMemcpy(contour4, P.contour_dev + O.contour_off, sizeof(float4) * nc, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------ PbMap persistence
 // Frame360::savePlanes / loadPbMap (Frame360.h:195-210, 312-318) stream the mrpt::pbmap::PbMap
 // through MRPT's CSerializable into a gzip file.  MRPT is not vendored in the reference, so its byte

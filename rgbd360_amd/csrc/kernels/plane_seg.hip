@@ -2524,6 +2524,33 @@ int launch_plane_publish(const PlaneBatch& B, int F, hipStream_t st) {
     return 0;
 }
 
+namespace {
+// r360_frame_segment_eval's inputs as the stage's first kernels leave theirs: points {x, y, z, 0}; normals
+// {nx, ny, nz, p.n} with p.n as normal_out (plane_kernels.hip) computes it, or all NaN where no normal is given
+__global__ void k_segment_inputs(const PlaneBatch B, long total) {
+    const PlaneDev& D = B.f[blockIdx.z];
+    if (blockIdx.x == 0 && threadIdx.x == 0) *D.err = 0;
+    const float nan = __builtin_nanf("");
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        float4 p = D.cloud[i];
+        p.w = 0.f;
+        D.cloud[i] = p;
+        const float4 n = D.nrm[i];
+        float4 o = make_float4(nan, nan, nan, nan);
+        if (isfin(n.x) && isfin(n.y) && isfin(n.z)) o = make_float4(n.x, n.y, n.z, p.x * n.x + p.y * n.y + p.z * n.z);
+        D.nrm[i] = o;
+    }
+}
+}  // namespace
+
+int launch_segment_inputs(const PlaneBatch& B, int F, const PlaneGeom& G, hipStream_t st) {
+    const long total = 8L * G.w * G.h;
+    const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_segment_inputs, dim3(blocks, 1, (unsigned)F), dim3(256), 0, st, B, total);
+    R360_HIP(hipGetLastError());
+    return 0;
+}
+
 // Test hook: refine()'s two sweeps on given states / closeness masks of 8 sensors (w x h each): rb = -1 the
 // wavefront sweeps (pipelined bands for h <= 512), -2 the barrier-per-diagonal wavefront, 0 the single-wave sweeps, rb > 0 banded with rb rows per band; out receives the swept
 // states.  Returns the number of sensors whose wavefront second sweep needed wrap-push corrections (re-runs

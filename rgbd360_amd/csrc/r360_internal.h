@@ -641,6 +641,9 @@ int launch_rgb(const PlaneBatch& B, int F, const PlaneGeom& G, hipStream_t st); 
 int launch_segmentation_geom(const PlaneBatch& B, int F, const PlaneGeom& G, hipStream_t st, r360_ctx* tctx);
 int launch_segmentation_model(const PlaneBatch& B, int F, const PlaneGeom& G, hipStream_t st, r360_ctx* tctx);
 int launch_plane_publish(const PlaneBatch& B, int F, hipStream_t st);   // plane outputs -> pinned host buffers
+// r360_frame_segment_eval: given points and normals (already in cloud / nrm) made what k_cloud / k_normals leave
+// (point w = 0, normal w = p.n or all NaN), and the error word zeroed as k_plane_begin does
+int launch_segment_inputs(const PlaneBatch& B, int F, const PlaneGeom& G, hipStream_t st);
 // voxel-fallback scratch the plane stage of one frame uses (its context's, or a plane queue slot's)
 struct VoxScratch { VoxCell* vhash; unsigned long long cap; int* vlist; int* vcnt; };
 // the voxel scratch sizes a frame of G needs: hash cells, list entries, list groups (workgroups)

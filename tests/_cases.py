@@ -91,3 +91,169 @@ def room_sphere(rows, cols, eye, seed, holes=0.1):
 def room_pair(rows, cols):
     """(target images, source images) of the room at rows x cols."""
     return room_sphere(rows, cols, *ROOM_TARGET), room_sphere(rows, cols, *ROOM_SOURCE)
+
+
+# ------------------------------------------------------------------ plane half: shared comparisons and inputs
+def same(a, b):
+    """bitwise equality with NaN == NaN"""
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
+
+
+def per_sensor_oracle(b, dm):
+    """The oracle's per-pixel stages and segmentation of the 8 sensors of one frame (BGR images, depth in metres)."""
+    from oracle import oracle360 as O
+    out = []
+    for k in range(8):
+        xyz, rgb = O.cloud_downsample(dm[k], b[k])
+        xf = O.bilateral(xyz)
+        nrm, dist = O.normals(xf)
+        lc, lf, regs = O.segment(xf, nrm)
+        out.append(dict(xyz=xf, rgb=rgb, nrm=nrm, dist=dist, lc=lc, lf=lf, regs=regs))
+    return out
+
+
+def cmp_per_pixel(f, ref):
+    """Frame f's per-pixel stages and region records against per_sensor_oracle's: cloud, colours, distance map below
+    the 9.5 cap it is consumed at, normals, CCL labels, refined labels and every region field, bit for bit."""
+    xyz, rgb, nrm, dist = f.cloud()
+    lab, labf = f.labels()
+    for k in range(8):
+        r = ref[k]
+        assert same(xyz[k], r["xyz"]), ("cloud", k)
+        assert np.array_equal(rgb[k], r["rgb"]), ("rgb", k)
+        assert same(np.minimum(dist[k], 9.5), np.minimum(r["dist"], 9.5)), ("dist", k)
+        assert same(nrm[k][..., :3], r["nrm"][..., :3]), ("normals", k)
+        assert np.array_equal(lab[k], r["lc"]), ("ccl", k)
+        assert np.array_equal(labf[k], r["lf"]), ("refined labels", k)
+        cmp_regions(f.regions(k), r["regs"], k)
+
+
+def cmp_regions(regs, oregs, k=None, nan_equal=False):
+    """nan_equal: NaN == NaN in the float fields (crafted fields whose regions are lines: the fit of a rank-1
+    covariance is NaN in the reference too)."""
+    eq = same if nan_equal else np.array_equal
+    assert len(regs) == len(oregs), ("regions", k)
+    for g, o in zip(regs, oregs):
+        assert (g["label"], g["count"], g["start_idx"], g["n_contour"]) == \
+            (o["label"], o["count"], o["start_idx"], len(o["contour"])), ("region", k)
+        for key in ("centroid", "cov", "model"):
+            assert eq(g[key], o[key]), (key, k, g[key], o[key])
+        assert eq(g["curvature"], o["curvature"]), (k, g["curvature"], o["curvature"])
+
+
+def cmp_planes(gp, op):
+    assert len(gp) == len(op)
+    for g, o in zip(gp, op):
+        for key in ("normal", "center", "ppal", "nrgb", "hull"):
+            assert np.array_equal(g[key], o[key]), key
+        for key in ("d", "area", "elongation", "curvature", "intensity", "id", "sensor", "n_inliers"):
+            assert g[key] == o[key], key
+
+
+# ------------------------------------------------------------------ plane half: ragged sensors and crafted fields
+# sensor rows x cols of tests/test_gpu_plane_shapes.py (the organized clouds are rows/2 x cols/2)
+PLANE_SHAPES = [(66, 90), (130, 250), (34, 400), (258, 70), (32, 162), (100, 132), (194, 258), (512, 768), (516, 768)]
+PLANE_SEEDS = (360 << 16, (360 << 16) + 7)
+
+
+def plane_pair_rel():
+    """The second pose of the synthetic pairs relative to the first: 4 degrees about x and (0, 0.25, 0.15) m."""
+    rel = np.eye(4, dtype=np.float32)
+    a = np.deg2rad(4.0)
+    rel[1:3, 1:3] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+    rel[:3, 3] = [0, 0.25, 0.15]
+    return rel
+
+
+def depth_metres(depth_mm):
+    """A calibration without intrinsic models leaves depth_m = mm * 0.001f."""
+    return depth_mm.astype(np.float32) * np.float32(0.001)
+
+
+def stripe_sensor(h, w, sw, band=0, phase=0, flip=0):
+    """One sensor's organized cloud [h, w, 4] and exact unit normals [h, w, 3] of vertical stripes sw pixels wide (the
+    first one sw - phase wide), optionally cut into horizontal bands of `band` rows.  Pixel (v, u) looks along the
+    pinhole ray ((u - cx) / f, (v - cy) / f, 1) with f = 525 (2 w / 640) / 2 and centre (w / 2 - 0.5, h / 2 - 0.5);
+    stripe k of band b lies on the plane n . p = -2 with n = normalize((+-0.15, 0, -1)), the sign alternating with
+    k + b + flip.  Neighbouring stripes' normals differ by 17 degrees (the comparator's threshold is 2.3), so every
+    stripe is a label of its own; sw = 0: one plane over the whole sensor."""
+    f = 525.0 * (2 * w / 640.0) / 2
+    cx, cy = w / 2 - 0.5, h / 2 - 0.5
+    v, u = np.mgrid[0:h, 0:w]
+    k = (u + phase) // sw if sw else np.zeros_like(u)
+    if band:
+        k = k + v // band
+    sgn = np.where((k + flip) % 2 == 0, 1.0, -1.0)
+    ln = np.sqrt(0.15 ** 2 + 1.0)
+    n = np.stack([sgn * 0.15 / ln, np.zeros_like(sgn), np.full_like(sgn, -1.0 / ln)], -1)
+    ray = np.stack([(u - cx) / f, (v - cy) / f, np.ones((h, w))], -1)
+    z = -2.0 / np.einsum("ijk,ijk->ij", ray, n)
+    xyz = np.zeros((h, w, 4), np.float32)
+    xyz[..., :3] = ray * z[..., None]
+    return xyz, n.astype(np.float32)
+
+
+# the crafted fields of tests/test_gpu_plane_shapes.py: cloud h x w, stripe width, band rows, and the sensors'
+# (kind, phase, flip): "s" striped, "p" one plane, "n" all NaN
+STRIPE_CASES = {
+    # 40 stripes of 84 pixels per striped sensor; sensors 0 and 1 alike, so the 512-pixel span over their seam holds
+    # 80 keys (more than the 64 slots of k_gm's table)
+    "a": dict(h=21, w=160, sw=4, band=0, sensors=[("s", 0, 0), ("s", 0, 0), ("n", 0, 0), ("p", 0, 0), ("s", 1, 0),
+                                                   ("s", 2, 1), ("n", 0, 0), ("s", 3, 0)]),
+    # 64 one-pixel stripes of 81 pixels: exactly R360_MAX_MODELS models
+    "b": dict(h=81, w=64, sw=1, band=0, sensors=[("s", 0, 0), ("n", 0, 0), ("s", 0, 1), ("p", 0, 0), ("s", 0, 0),
+                                                  ("s", 0, 1), ("n", 0, 0), ("s", 0, 0)]),
+    # 60 one-pixel stripes of 200 pixels: 23 940 contour points per striped sensor (> TR_LIST)
+    "c": dict(h=200, w=60, sw=1, band=0, sensors=[("s", 0, 0), ("p", 0, 0), ("n", 0, 0), ("s", 0, 1), ("s", 0, 0),
+                                                   ("n", 0, 0), ("s", 0, 1), ("s", 0, 0)]),
+    # 70 models: error bit 4
+    "d": dict(h=81, w=70, sw=1, band=0, sensors=[("s", 0, 0), ("n", 0, 0), ("p", 0, 0), ("s", 0, 1), ("s", 0, 0),
+                                                  ("s", 0, 1), ("n", 0, 0), ("s", 0, 0)]),
+    # 640 labels above 80 points: error bit 2
+    "e": dict(h=240, w=320, sw=1, band=81, sensors=[("s", 0, 0), ("n", 0, 0), ("p", 0, 0), ("s", 0, 1), ("s", 0, 0),
+                                                     ("s", 0, 1), ("n", 0, 0), ("s", 0, 0)]),
+}
+
+
+def stripe_frame(case, h=None, w=None, sw=None):
+    """The 8 sensors' fields of STRIPE_CASES[case] (at another cloud size h x w or stripe width if given): (xyz4 [8, h, w, 4],
+    normals [8, h, w, 3], rgb4 [8, h, w, 4] with fixed pseudo-random bytes and a zero fourth byte)."""
+    c = STRIPE_CASES[case]
+    h, w, sw = h or c["h"], w or c["w"], sw or c["sw"]
+    xyz = np.zeros((8, h, w, 4), np.float32)
+    nrm = np.zeros((8, h, w, 3), np.float32)
+    for s, (kind, phase, flip) in enumerate(c["sensors"]):
+        if kind == "n":
+            xyz[s, ..., :3] = np.nan
+            nrm[s] = np.nan
+        else:
+            xyz[s], nrm[s] = stripe_sensor(h, w, sw if kind == "s" else 0, c["band"] if kind == "s" else 0,
+                                           phase, flip)
+    rgb = np.random.default_rng(4242).integers(0, 256, (8, h, w, 4), dtype=np.uint8)
+    rgb[..., 3] = 0
+    rgb[0, 0, :4, :3] = 0          # black pixels: moments_add_rgb's zero-sum branch
+    return xyz, nrm, rgb
+
+
+def stripe_oracle(xyz, nrm):
+    """O.segment per sensor of a crafted frame: [(labels, refined labels, regions)] * 8."""
+    from oracle import oracle360 as O
+    out = []
+    for s in range(8):
+        n4 = np.zeros(xyz[s].shape, np.float32)
+        n4[..., :3] = nrm[s]
+        out.append(O.segment(xyz[s], n4, max_regions=1024))
+    return out
+
+
+def span_keys(labels8, keyed8, px=512):
+    """Distinct (sensor, label) keys per span of `px` consecutive pixels of the 8 sensors' label images taken as one
+    array (k_gm's workgroups): labels8 [8, h, w]; keyed8[s] = the labels of sensor s that have a key."""
+    flat = labels8.reshape(8, -1)
+    n = flat.shape[1]
+    key = np.full(8 * n, -1, np.int64)
+    for s in range(8):
+        ok = np.isin(flat[s], np.asarray(sorted(keyed8[s]), np.int64))
+        key[s * n:(s + 1) * n] = np.where(ok, s * n + flat[s], -1)
+    return [len(set(key[i:i + px].tolist()) - {-1}) for i in range(0, 8 * n, px)]

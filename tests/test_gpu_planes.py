@@ -13,13 +13,9 @@ import pytest
 
 import rgbd360_amd as R
 from oracle import oracle360 as O
+from _cases import cmp_per_pixel, cmp_planes as _cmp_planes, per_sensor_oracle as _per_sensor_oracle, same as _same
 
 pytestmark = pytest.mark.gpu
-
-def _same(a, b):
-    """bitwise equality with NaN == NaN"""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
 
 
 @pytest.fixture(scope="module")
@@ -102,49 +98,11 @@ def test_latency_mode_is_result_neutral(vga):
             _cmp_planes(f.planes(), ref.planes())
 
 
-def _per_sensor_oracle(b, dm):
-    out = []
-    for k in range(8):
-        xyz, rgb = O.cloud_downsample(dm[k], b[k])
-        xf = O.bilateral(xyz)
-        nrm, dist = O.normals(xf)
-        lc, lf, regs = O.segment(xf, nrm)
-        out.append(dict(xyz=xf, rgb=rgb, nrm=nrm, dist=dist, lc=lc, lf=lf, regs=regs))
-    return out
-
-
 @pytest.mark.parametrize("which", ["qvga", "vga"])
 def test_per_pixel_stages_bitexact(request, which):
     D = request.getfixturevalue(which)
     for f, (b, dm) in zip(D["frames"], D["inputs"]):
-        xyz, rgb, nrm, dist = f.cloud()
-        lab, labf = f.labels()
-        ref = _per_sensor_oracle(b, dm)
-        for k in range(8):
-            r = ref[k]
-            assert _same(xyz[k], r["xyz"]), ("cloud", k)
-            assert np.array_equal(rgb[k], r["rgb"]), ("rgb", k)
-            assert _same(np.minimum(dist[k], 9.5), np.minimum(r["dist"], 9.5)), ("dist", k)
-            assert _same(nrm[k][..., :3], r["nrm"][..., :3]), ("normals", k)
-            assert np.array_equal(lab[k], r["lc"]), ("ccl", k)
-            assert np.array_equal(labf[k], r["lf"]), ("refined labels", k)
-            regs = f.regions(k)
-            assert len(regs) == len(r["regs"]), ("regions", k)
-            for g, o in zip(regs, r["regs"]):
-                assert (g["label"], g["count"], g["start_idx"], g["n_contour"]) == \
-                    (o["label"], o["count"], o["start_idx"], len(o["contour"])), ("region", k)
-                for key in ("centroid", "cov", "model"):
-                    assert np.array_equal(g[key], o[key]), (key, k)
-                assert g["curvature"] == o["curvature"]
-
-
-def _cmp_planes(gp, op):
-    assert len(gp) == len(op)
-    for g, o in zip(gp, op):
-        for key in ("normal", "center", "ppal", "nrgb", "hull"):
-            assert np.array_equal(g[key], o[key]), key
-        for key in ("d", "area", "elongation", "curvature", "intensity", "id", "sensor", "n_inliers"):
-            assert g[key] == o[key], key
+        cmp_per_pixel(f, _per_sensor_oracle(b, dm))
 
 
 @pytest.mark.parametrize("which", ["qvga", "vga"])
