@@ -29,6 +29,7 @@
 
 using r360::Calib360;
 using r360::FilterPointCloud;
+using r360::GeneralizedIterativeClosestPoint;
 using r360::Frame360;
 using r360::PbMap;
 using r360::Plane;

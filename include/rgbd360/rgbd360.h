@@ -804,4 +804,51 @@ inline bool GlobalMap360::add(Frame360& keyframe, const Matrix4f& pose) {
                  "GlobalMap360::add") == 0;
 }
 
+// ------------------------------------------------------------------ Generalized-ICP
+// pcl::GeneralizedIterativeClosestPoint with the call surface of Registration/RegisterPairRGBD360.cpp:109-149, on the
+// GPU of the calling thread's default context or of the Context given (r360_gicp_*; the algorithm is restated, with a
+// Gauss-Newton inner solve where PCL runs BFGS: DESIGN.md §5c).  The clouds live in the context: one source and one
+// target per context at a time.  setRANSACOutlierRejectionThreshold stores its value and nothing reads it, as in
+// PCL's GICP, whose computeTransformation never runs the RANSAC rejector.
+class GeneralizedIterativeClosestPoint {
+  public:
+    GeneralizedIterativeClosestPoint() : keep_(default_context_ptr()), ctx_(keep_.get()) { r360_gicp_default_params(&p_); }
+    explicit GeneralizedIterativeClosestPoint(Context& ctx) : ctx_(&ctx) { r360_gicp_default_params(&p_); }
+    void setMaxCorrespondenceDistance(double d) { p_.max_corr_dist = float(d); }
+    void setMaximumIterations(int n) { p_.max_iterations = n; }
+    void setTransformationEpsilon(double e) { p_.transformation_epsilon = e; }
+    void setRotationEpsilon(double e) { p_.rotation_epsilon = e; }
+    void setCorrespondenceRandomness(int k) { p_.k_correspondences = k; }
+    void setMaximumOptimizerIterations(int n) { p_.max_inner_iterations = n; }
+    void setRANSACOutlierRejectionThreshold(double t) { ransac_ = t; }
+    double getRANSACOutlierRejectionThreshold() const { return ransac_; }
+    // rows with a non-finite coordinate are dropped; fewer than k finite points throws (as PCL does)
+    void setInputSource(const PointCloud& cloud) {
+        src_ = &cloud;
+        check(r360_gicp_set_source(ctx_->get(), cloud.xyz.data(), cloud.size(), &p_), "GICP setInputSource");
+    }
+    void setInputTarget(const PointCloud& cloud) {
+        check(r360_gicp_set_target(ctx_->get(), cloud.xyz.data(), cloud.size(), &p_), "GICP setInputTarget");
+    }
+    // out: the source cloud under the final transformation (the cloud given to setInputSource must still exist)
+    void align(PointCloud& out, const Matrix4f& guess = Matrix4f::Identity()) {
+        illposed_ = check(r360_gicp_align(ctx_->get(), guess.data(), &p_, T_.data(), &st_), "GICP align") == 1;
+        if (src_) transformPointCloud(*src_, out, T_);
+    }
+    Matrix4f getFinalTransformation() const { return T_; }
+    bool hasConverged() const { return st_.converged != 0; }
+    double getFitnessScore() const { return st_.fitness; }
+    bool illPosed() const { return illposed_; }   // no pair inside the gate or a singular system: the pose stayed
+    const r360_gicp_stats& stats() const { return st_; }
+  private:
+    std::shared_ptr<Context> keep_;
+    Context* ctx_;
+    r360_gicp_params p_;
+    r360_gicp_stats st_ = r360_gicp_stats();
+    const PointCloud* src_ = nullptr;
+    Matrix4f T_ = Matrix4f::Identity();
+    double ransac_ = 0.05;
+    bool illposed_ = false;
+};
+
 }  // namespace r360

@@ -707,6 +707,46 @@ int r360_ctx_map_add_frame(r360_ctx* ctx, r360_frame* f, const float pose[16], f
 int r360_ctx_map_size(r360_ctx* ctx, size_t* n);
 int r360_ctx_map_download(r360_ctx* ctx, float* xyz, uint32_t* rgba, size_t cap, size_t* n);
 
+/* ---------------------------------------------------------------- Generalized-ICP
+ * pcl::GeneralizedIterativeClosestPoint as Registration/RegisterPairRGBD360.cpp:109-149 calls it, restated (PCL is
+ * not pinned): the statement is tests/gicp_model.py and DESIGN.md §5c.  Per cloud: rows with a non-finite coordinate
+ * are dropped (order kept), every point's k nearest points of its own cloud (itself included, ties to the lower
+ * index) give C_i = V diag(gicp_epsilon, 1, 1) V^T.  Per outer iteration: the nearest target of every transformed
+ * source point (squared distance strictly below max_corr_dist^2), M_i = (Ct_j + R Cs_i R^T)^-1, then a Gauss-Newton
+ * inner solve of sum r^T M r with left SE(3) increments (r360_exp_se3, pseudo = 0), where PCL runs BFGS.
+ * Poses are column-major 4x4 and map source into target.  The clouds, their indices and every pass buffer belong to
+ * the context and are freed by r360_ctx_destroy; a new source or target of any size may be set at any time.
+ * set_source / set_target: < 0 with fewer than k_correspondences finite points (PCL throws) or k_correspondences
+ * outside 4 .. 32.  align: 0, or 1 (R360_ILLPOSED's value) when no pair passes the gate or the first 6x6 system of
+ * an outer iteration is singular: pose_out is then the pose reached so far (init at the first iteration). */
+typedef struct {
+    int k_correspondences;          /* 20 */
+    float gicp_epsilon;             /* 1e-3 */
+    float max_corr_dist;            /* 0.4 (the reference program's) */
+    int max_iterations;             /* 10 (the reference program's) */
+    int max_inner_iterations;       /* 20 */
+    double rotation_epsilon;        /* 2e-3 */
+    double transformation_epsilon;  /* 1e-9 (the reference program's) */
+} r360_gicp_params;
+typedef struct {
+    int iterations, converged, inner_steps;   /* outer iterations, the epsilon test met, accepted inner steps in all */
+    size_t n_corr;                            /* correspondences of the last outer iteration */
+    double cost, fitness;                     /* f / n_corr there; mean squared nearest-target distance of all
+                                                 source points at the final pose (getFitnessScore, no range limit) */
+} r360_gicp_stats;
+void r360_gicp_default_params(r360_gicp_params* p);
+int r360_gicp_set_source(r360_ctx* ctx, const float* xyz, size_t n, const r360_gicp_params* p);
+int r360_gicp_set_target(r360_ctx* ctx, const float* xyz, size_t n, const r360_gicp_params* p);
+int r360_gicp_align(r360_ctx* ctx, const float init[16], const r360_gicp_params* p, float pose_out[16],
+                    r360_gicp_stats* stats);
+/* Parity hooks.  get_cloud: which = 0 source, 1 target; the kept points (3 floats each), the upper triangles
+ * xx xy xz yy yz zz of C_i as float and the k neighbour indices per point in ascending (distance, index) order; any
+ * output may be NULL; cap = room in points; *n is set either way.  eval: one correspondence pass and one inner pass
+ * at `pose`: corr[i] = j(i) or -1 per kept source point (may be NULL), *cost = f (the sum), H row-major, g. */
+int r360_gicp_get_cloud(r360_ctx* ctx, int which, float* xyz, float* cov6, int* knn, size_t cap, size_t* n);
+int r360_gicp_eval(r360_ctx* ctx, const float pose[16], const r360_gicp_params* p, int* corr, double* cost,
+                   double H[36], double g[6], size_t* n_corr);
+
 #ifdef __cplusplus
 }
 #endif

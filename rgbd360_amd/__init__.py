@@ -25,6 +25,7 @@ C = C  # re-exported for callers that drive the C-ABI directly (bench.py)
 
 __all__ = [
     "lib", "Context", "Calib360", "Frame360", "RegisterPhotoICP", "RegisterRGBD360", "IcpParams", "IcpStats",
+    "GicpParams", "GicpStats", "GeneralizedICP",
     "PHOTO_CONSISTENCY", "DEPTH_CONSISTENCY", "PHOTO_DEPTH", "synth_path_pose", "exp_se3",
     "LIB_PATH", "ABI_SYMBOLS", "Batch", "PairJob", "PairResult", "JOB_PBMAP_ONLY", "JOB_GATED", "JOB_ALWAYS",
 ]
@@ -54,6 +55,29 @@ class IcpParams(C.Structure):
         p = cls()
         lib().r360_icp_default_params(C.byref(p))
         return p
+
+
+class GicpParams(C.Structure):
+    """r360_gicp_params — Generalized-ICP settings under PCL's names (see include/rgbd360_hip.h)."""
+    _fields_ = [
+        ("k_correspondences", C.c_int), ("gicp_epsilon", C.c_float), ("max_corr_dist", C.c_float),
+        ("max_iterations", C.c_int), ("max_inner_iterations", C.c_int), ("rotation_epsilon", C.c_double),
+        ("transformation_epsilon", C.c_double),
+    ]
+
+    @classmethod
+    def default(cls) -> "GicpParams":
+        p = cls()
+        lib().r360_gicp_default_params(C.byref(p))
+        return p
+
+
+class GicpStats(C.Structure):
+    """r360_gicp_stats — what one r360_gicp_align did."""
+    _fields_ = [
+        ("iterations", C.c_int), ("converged", C.c_int), ("inner_steps", C.c_int), ("n_corr", C.c_size_t),
+        ("cost", C.c_double), ("fitness", C.c_double),
+    ]
 
 
 class MatchParams(C.Structure):
@@ -304,6 +328,12 @@ _SIGS = [
     ("r360_ctx_map_add_frame", C.c_int, [_P, _P, _FP, C.c_float, C.c_float, C.c_float, C.c_float]),
     ("r360_ctx_map_size", C.c_int, [_P, C.POINTER(C.c_size_t)]),
     ("r360_ctx_map_download", C.c_int, [_P, _FP, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_gicp_default_params", None, [C.POINTER(GicpParams)]),
+    ("r360_gicp_set_source", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
+    ("r360_gicp_set_target", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
+    ("r360_gicp_align", C.c_int, [_P, _FP, C.POINTER(GicpParams), _FP, C.POINTER(GicpStats)]),
+    ("r360_gicp_get_cloud", C.c_int, [_P, C.c_int, _FP, _FP, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_gicp_eval", C.c_int, [_P, _FP, C.POINTER(GicpParams), _IP, _DP, _DP, _DP, C.POINTER(C.c_size_t)]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -487,6 +517,54 @@ class Context:
         rgba = np.zeros(n.value, np.uint32)
         _check(lib().r360_ctx_map_download(self.h, _fptr(xyz), _vptr(rgba), n.value, C.byref(n)), "map_download")
         return xyz, rgba
+
+    def _gicp_set(self, fn, xyz, params, what):
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        p = params if params is not None else GicpParams.default()
+        _check(fn(self.h, _fptr(xyz), xyz.shape[0], C.byref(p)), what)
+
+    def gicp_set_source(self, xyz, params: "GicpParams | None" = None):
+        """The Generalized-ICP source cloud ([n,3] float32): non-finite rows dropped, grid index, kNN covariances."""
+        self._gicp_set(lib().r360_gicp_set_source, xyz, params, "gicp_set_source")
+
+    def gicp_set_target(self, xyz, params: "GicpParams | None" = None):
+        """The Generalized-ICP target cloud (as gicp_set_source)."""
+        self._gicp_set(lib().r360_gicp_set_target, xyz, params, "gicp_set_target")
+
+    def gicp_align(self, init=None, params: "GicpParams | None" = None):
+        """r360_gicp_align from `init` (4x4, source into target).  Returns (pose 4x4 float32, GicpStats, status);
+        status 1: ill-posed (no pair inside the gate or a singular system), the pose is the one reached so far."""
+        p = params if params is not None else GicpParams.default()
+        out = np.zeros(16, np.float32)
+        st = GicpStats()
+        rc = _check(lib().r360_gicp_align(self.h, _fptr(_mat16(np.eye(4) if init is None else init)), C.byref(p),
+                                          _fptr(out), C.byref(st)), "gicp_align")
+        return _from16(out), st, rc
+
+    def gicp_eval(self, pose, params: "GicpParams | None" = None):
+        """One correspondence pass and one inner pass at `pose` (r360_gicp_eval): (corr [n] int32 with -1 for none,
+        cost f, H [6,6], g [6], n_corr), the sums in double."""
+        p = params if params is not None else GicpParams.default()
+        n = C.c_size_t()
+        _check(lib().r360_gicp_get_cloud(self.h, 0, None, None, None, 0, C.byref(n)), "gicp_get_cloud")
+        corr = np.zeros(n.value, np.int32)
+        cost, nc = C.c_double(), C.c_size_t()
+        H, g = np.zeros(36, np.float64), np.zeros(6, np.float64)
+        _check(lib().r360_gicp_eval(self.h, _fptr(_mat16(pose)), C.byref(p), corr.ctypes.data_as(_IP), C.byref(cost),
+                                    _dptr(H), _dptr(g), C.byref(nc)), "gicp_eval")
+        return corr, cost.value, H.reshape(6, 6), g, nc.value
+
+    def gicp_cloud(self, which: int, k: int = 20):
+        """The kept points of the source (0) or target (1) cloud, their covariances' upper triangles [n,6] float32
+        and the kNN index lists [n,k] (k: the k_correspondences the cloud was set with)."""
+        n = C.c_size_t()
+        _check(lib().r360_gicp_get_cloud(self.h, which, None, None, None, 0, C.byref(n)), "gicp_get_cloud")
+        xyz = np.zeros((n.value, 3), np.float32)
+        cov = np.zeros((n.value, 6), np.float32)
+        knn = np.zeros((n.value, k), np.int32)
+        _check(lib().r360_gicp_get_cloud(self.h, which, _fptr(xyz), _fptr(cov), knn.ctypes.data_as(_IP), n.value,
+                                         C.byref(n)), "gicp_get_cloud")
+        return xyz, cov, knn
 
     def close(self):
         if self.h:
@@ -1489,3 +1567,47 @@ DATA_DIR = os.path.join(REPO_ROOT, "data")
 EXTRINSICS_DIR = os.path.join(DATA_DIR, "calib", "Extrinsics")   # Rt_0{1..8}.txt (reference rig)
 INTRINSICS_DIR = os.path.join(DATA_DIR, "calib", "Intrinsics")   # CLAMS tables (compact form)
 SAMPLES_DIR = os.path.join(DATA_DIR, "samples")                  # sphere_images_{1,10}.bin
+
+
+class GeneralizedICP:
+    """r360::GeneralizedIterativeClosestPoint's Python mirror: pcl::GeneralizedIterativeClosestPoint's call surface
+    as Registration/RegisterPairRGBD360.cpp:109-149 uses it, over Context.gicp_*.  Clouds are [n,3] float32."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self.params = GicpParams.default()
+        self.ransac_threshold = 0.05   # stored and never read, as in PCL's GICP
+        self.stats = GicpStats()
+        self._pose = np.eye(4, dtype=np.float32)
+        self._src = None
+        self._status = 0
+
+    def setMaxCorrespondenceDistance(self, d: float): self.params.max_corr_dist = d
+    def setMaximumIterations(self, n: int): self.params.max_iterations = n
+    def setTransformationEpsilon(self, e: float): self.params.transformation_epsilon = e
+    def setRotationEpsilon(self, e: float): self.params.rotation_epsilon = e
+    def setCorrespondenceRandomness(self, k: int): self.params.k_correspondences = k
+    def setMaximumOptimizerIterations(self, n: int): self.params.max_inner_iterations = n
+    def setRANSACOutlierRejectionThreshold(self, t: float): self.ransac_threshold = t
+
+    def setInputSource(self, xyz):
+        self._src = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self.ctx.gicp_set_source(self._src, self.params)
+
+    def setInputTarget(self, xyz):
+        self.ctx.gicp_set_target(xyz, self.params)
+
+    def align(self, guess=None) -> np.ndarray:
+        """Runs the registration and returns the source cloud under the final transformation (float, left to right,
+        as transformPointCloud)."""
+        self._pose, self.stats, self._status = self.ctx.gicp_align(guess, self.params)
+        m = self._pose
+        s = self._src
+        out = np.empty_like(s)
+        for k in range(3):
+            out[:, k] = ((m[k, 0] * s[:, 0] + m[k, 1] * s[:, 1]) + m[k, 2] * s[:, 2]) + m[k, 3]
+        return out
+
+    def getFinalTransformation(self) -> np.ndarray: return self._pose.copy()
+    def hasConverged(self) -> bool: return bool(self.stats.converged)
+    def getFitnessScore(self) -> float: return self.stats.fitness

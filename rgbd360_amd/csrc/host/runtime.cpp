@@ -308,6 +308,7 @@ extern "C" void r360_ctx_destroy(r360_ctx* c) {
     hipFree(c->d_vlist); hipFree(c->d_vcnt);
     for (auto& s : c->bvox) vox_slot_free(s);
     map_state_free(c->vmap);   // voxel-filter scratch and the context's global map
+    gicp_state_free(c->gicp);  // Generalized-ICP clouds and pass buffers
     hipHostFree(c->h_unary); hipHostFree(c->h_bin);
     if (c->up_stream) {
         hipStreamSynchronize(c->up_stream);

@@ -9,6 +9,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/rgbd360_hip.h"
+#include "host/gicp_host.h"
 
 #define R360_PI 3.14159265359  // include/Miscellaneous.h:44 (double literal)
 
@@ -354,11 +355,48 @@ int launch_map_finalise(hipStream_t st, const uint4* pts, size_t n, MapCell* tab
                         uint4* out, size_t out_cap);
 int launch_map_unpack(hipStream_t st, const uint4* pts, size_t m, float* xyz, uint32_t* rgba);
 
+// ------------------------------------------------------------------ Generalized-ICP (kernels/gicp_kernels.hip, host/gicp.cpp)
+// GicpGrid, the uniform grid over a cloud's bounding box, and the host-only logic: host/gicp_host.h
+constexpr int R360_GICP_KMAX = 32;      // k_correspondences the kNN kernel's LDS lists hold
+constexpr int R360_GICP_W = 29;         // one inner pass's sums: f, g (6), H upper triangle (21), n_corr
+constexpr int R360_GICP_MAXB = 256;     // workgroups (= partial records) of the inner pass at most
+struct GicpCloud {
+    size_t n = 0, cap = 0, spts_cap = 0, cov_cap = 0, cells = 0, cells_cap = 0;
+    int k = 0;
+    GicpGrid grid{};
+    float4* pts = nullptr;              // kept points in input order {x, y, z, 0}
+    float4* spts = nullptr;             // the same points ordered by cell, w = the point's index (bits)
+    unsigned* cell_start = nullptr;     // [cells + 1] first sorted point of every cell
+    double* cov6 = nullptr;             // [n][6] upper triangle xx xy xz yy yz zz of C_i (fp64: M_i inverts sums of them)
+    int* knn = nullptr;                 // [n][k] neighbour indices, ascending (distance, index)
+    size_t knn_cap = 0;
+};
+struct GicpPose { double m[12]; };      // row-major 3 x 4 [R | t]
+struct GicpState {
+    GicpCloud src, tgt;
+    int* corr = nullptr;                // [src.n] j(i), -1 = none
+    double* M6 = nullptr;               // [src.n][6] upper triangle of M_i
+    double* d2 = nullptr;               // [src.n] squared distance to j(i)
+    size_t corr_cap = 0;
+    double* partials = nullptr;         // [R360_GICP_MAXB][R360_GICP_W]
+    double* d_sums = nullptr;           // [R360_GICP_W]
+    double* h_sums = nullptr;           // pinned
+};
+void gicp_state_free(GicpState& S);
+int launch_gicp_knn_cov(hipStream_t st, const GicpCloud& C, float eps);
+int launch_gicp_corr(hipStream_t st, const GicpCloud& S, const GicpCloud& T, const GicpPose& X, double gate2, int want_m,
+                     int* corr, double* M6, double* d2);
+int gicp_pass_blocks(size_t n);
+int launch_gicp_pass(hipStream_t st, const GicpCloud& S, const GicpCloud& T, const GicpPose& Y, const int* corr,
+                     const double* M6, double* partials, double* sums);
+int launch_gicp_sum(hipStream_t st, const double* v, size_t n, double* partials, double* sums);
+
 // ------------------------------------------------------------------ host objects
 struct r360_plane_queue;
 struct VoxSlot;
 struct r360_ctx {
     MapState vmap;                         // voxel-filter scratch and the context's global map (host/map.cpp)
+    GicpState gicp;                        // Generalized-ICP clouds, indices and pass buffers (host/gicp.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
     hipStream_t stream = nullptr;

@@ -1,0 +1,274 @@
+"""Generalized-ICP on the GPU (kernels/gicp_kernels.hip, host/gicp.cpp) against its numpy statement
+tests/gicp_model.py, on the inputs of tests/_gicp_cases.py.  Exact comparisons (kNN lists, correspondences) apply to
+the points a rounding cannot change ("decided", _gicp_cases); at most 1 % of a case's points may be undecided, and
+that is asserted.  Bars: |C_gpu - C_model| <= 2^-22 per entry (an fp64 eigenvector is off by at most about
+1e-14 * l2 / (l1 - l0) <= 1e-8 on decided points, the float32 store of an entry in [-1, 1] adds 2^-24); cost within
+1e-6 relative, H and g within 1e-5 of max |H| and max |g| (the project's bars for the dense passes); a whole
+alignment's pose within 1e-4 rad and 1e-3 m of the model's (the north-star bar), iterations and converged equal.
+
+Measured on the MI355X (printed by the tests): pose drift against the model at most 1.1e-9 rad and 4.4e-9 m, cost,
+H and g within 1.3e-13 of the model, covariances within 2.98e-8 (the float32 store of the hook's output)."""
+import functools
+import os
+import re
+import subprocess
+import threading
+
+import numpy as np
+import pytest
+
+import rgbd360_amd as R
+
+import _gicp_cases as GC
+import gicp_model as GM
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BAR_RAD, BAR_M = 1e-4, 1e-3
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = R.Context(0)
+    yield c
+    c.close()
+
+
+def _full(C6):
+    C = np.empty((C6.shape[0], 3, 3), np.float64)
+    for q, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        C[:, a, b] = C[:, b, a] = C6[:, q]
+    return C
+
+
+def _check_cloud(ctx, which, model, label):
+    xyz, cov, knn = ctx.gicp_cloud(which)
+    assert xyz.tobytes() == model.xyz.tobytes(), label
+    kd, cd = GC.knn_decided(model), GC.cov_decided(model)
+    n = model.xyz.shape[0]
+    assert (~kd).sum() <= GC.MAX_UNDECIDED * n and (~cd).sum() <= GC.MAX_UNDECIDED * n, label
+    assert np.array_equal(knn[kd], model.knn[kd]), label
+    err = np.abs(_full(cov) - model.C)[cd].max()
+    print(f"{label}: n={n} undecided knn {(~kd).sum()} cov {(~cd).sum()} max |C - C_model| = {err:.3g}")
+    assert err <= 2.0 ** -22, (label, err)
+
+
+def _set_pair(ctx, ns, nt):
+    s, t = GC.pair(ns, nt)
+    ctx.gicp_set_source(s)
+    ctx.gicp_set_target(t)
+    return GC.model_pair(ns, nt)
+
+
+@pytest.mark.parametrize("ns,nt", GC.SIZES)
+def test_cloud_stage(ctx, ns, nt):
+    ms, mt = _set_pair(ctx, ns, nt)
+    _check_cloud(ctx, 0, ms, f"source {ns}")
+    _check_cloud(ctx, 1, mt, f"target {nt}")
+
+
+def test_cloud_stage_non_finite_rows(ctx):
+    rng = np.random.default_rng(5)
+    s = GC.room(2050, 7)
+    rows = rng.choice(2050, 50, replace=False)
+    s[rows, rng.integers(0, 3, 50)] = np.array([np.nan, np.inf, -np.inf])[rng.integers(0, 3, 50)]
+    ctx.gicp_set_source(s)
+    m = GM.Cloud(s, GC.params32())
+    assert m.xyz.shape[0] == 2000
+    _check_cloud(ctx, 0, m, "non-finite rows")
+
+
+def test_cloud_stage_crowded_cell(ctx):
+    rng = np.random.default_rng(6)
+    s = GC.room(3000, 8)
+    s[:500] = (np.array([1.0, 0.5, -0.25]) + rng.uniform(0, 0.05, size=(500, 3))).astype(np.float32)
+    ctx.gicp_set_source(s)
+    _check_cloud(ctx, 0, GM.Cloud(s, GC.params32()), "crowded cell")
+
+
+def test_too_few_points_is_an_error(ctx):
+    with pytest.raises(RuntimeError, match="fewer than k_correspondences"):
+        ctx.gicp_set_source(GC.room(19, 1))
+
+
+def _check_eval(ctx, ms, mt, X, label):
+    p = GC.params32()
+    corr, f, H, g, nc = ctx.gicp_eval(X)
+    X32 = np.asarray(X, np.float32).astype(np.float64)   # the ABI's pose is float32
+    mcorr, mf, mH, mg, mn, d2, second = GM.eval_at(ms, mt, X32, p)
+    dec = GC.corr_decided(d2, second, p.max_corr_dist)
+    und = int((~dec).sum())
+    assert und <= GC.MAX_UNDECIDED * corr.shape[0], label
+    assert np.array_equal(corr[dec], mcorr[dec]), label
+    assert abs(nc - mn) <= und, (label, nc, mn)
+    assert nc == (corr >= 0).sum()
+    if mn == 0:
+        assert f == 0.0 and not H.any() and not g.any()
+        return nc
+    ef = abs(f - mf) / mf
+    eH = np.abs(H - mH).max() / np.abs(mH).max()
+    eg = np.abs(g - mg).max() / np.abs(mg).max()
+    print(f"{label}: n_corr {nc} (model {mn}, undecided {und}) cost rel {ef:.3g} H {eH:.3g} g {eg:.3g}")
+    assert ef <= 1e-6 and eH <= 1e-5 and eg <= 1e-5, (label, ef, eH, eg)
+    return nc
+
+
+@pytest.mark.parametrize("ns,nt", GC.SIZES)
+def test_eval_stage(ctx, ns, nt):
+    ms, mt = _set_pair(ctx, ns, nt)
+    nc = _check_eval(ctx, ms, mt, np.eye(4), f"eval ({ns},{nt}) identity")
+    if (ns, nt) == (64, 129):
+        assert 0 < nc < 64   # the partial-gate case
+    _check_eval(ctx, ms, mt, GC.pose2(), f"eval ({ns},{nt}) pose 2")
+
+
+def test_no_correspondence_is_ill_posed(ctx):
+    s, t = GC.pair(1999, 2113)
+    t = t + np.float32(10.0)
+    ctx.gicp_set_source(s)
+    ctx.gicp_set_target(t)
+    corr, f, H, g, nc = ctx.gicp_eval(np.eye(4))
+    assert nc == 0 and (corr == -1).all()
+    init = GM.exp_se3((0.01, 0.02, 0.03, 0.01, 0.0, 0.0)).astype(np.float32)
+    pose, st, rc = ctx.gicp_align(init)
+    assert rc == 1 and st.n_corr == 0 and st.iterations == 0 and not st.converged
+    assert pose.tobytes() == init.tobytes()
+    m = GM.Cloud(s, GC.params32()), GM.Cloud(t, GC.params32())
+    mf = GM.fitness(m[0], m[1], init.astype(np.float64))
+    assert abs(st.fitness - mf) <= 1e-6 * mf
+
+
+@functools.lru_cache(maxsize=None)
+def _model_align(ns, nt, second_pose):
+    ms, mt = GC.model_pair(ns, nt)
+    init = (GC.pose2() if second_pose else np.eye(4)).astype(np.float32).astype(np.float64)
+    return GM.align(ms, mt, init, GC.params32())
+
+
+def _stats_tuple(st):
+    return (st.iterations, st.converged, st.inner_steps, st.n_corr, st.cost, st.fitness)
+
+
+def _align(ctx, ns, nt, second_pose):
+    _set_pair(ctx, ns, nt)
+    return ctx.gicp_align(GC.pose2() if second_pose else np.eye(4))
+
+
+@pytest.mark.parametrize("ns,nt,second_pose", [(1999, 2113, False), (20011, 19997, False), (1999, 2113, True)])
+def test_alignment(ctx, ns, nt, second_pose):
+    pose, st, rc = _align(ctx, ns, nt, second_pose)
+    ref = _model_align(ns, nt, second_pose)
+    ms, mt = GC.model_pair(ns, nt)
+    dr = GM.rot_angle(pose, ref.pose)
+    dt = float(np.linalg.norm(pose[:3, 3].astype(np.float64) - ref.pose[:3, 3]))
+    eg = (GM.rot_angle(pose, GC.G()), float(np.linalg.norm(pose[:3, 3] - GC.G()[:3, 3])))
+    mg = (GM.rot_angle(ref.pose, GC.G()), float(np.linalg.norm(ref.pose[:3, 3] - GC.G()[:3, 3])))
+    mfit = GM.fitness(ms, mt, pose.astype(np.float64))
+    print(f"align ({ns},{nt}) pose2={second_pose}: drift {dr:.3g} rad {dt:.3g} m; iterations {st.iterations} "
+          f"(model {ref.iterations}) inner {st.inner_steps} (model {ref.inner_steps}) converged {st.converged}; "
+          f"vs G {eg[0]:.3g} rad {eg[1]:.3g} m (model {mg[0]:.3g}, {mg[1]:.3g}); fitness {st.fitness:.6g} "
+          f"(model at this pose {mfit:.6g})")
+    assert rc == 0 and ref.status == 0
+    assert dr <= BAR_RAD and dt <= BAR_M, (dr, dt)
+    assert st.iterations == ref.iterations and bool(st.converged) == ref.converged
+    assert eg[0] <= mg[0] + BAR_RAD and eg[1] <= mg[1] + BAR_M
+    assert abs(st.fitness - mfit) <= 1e-6 * mfit
+
+
+def test_same_alignment_twice_gives_the_same_bytes(ctx):
+    a = _align(ctx, 1999, 2113, False)
+    b = _align(ctx, 1999, 2113, False)
+    assert a[0].tobytes() == b[0].tobytes() and _stats_tuple(a[1]) == _stats_tuple(b[1]) and a[2] == b[2]
+    c = ctx.gicp_align(np.eye(4))   # and without setting the clouds again
+    assert a[0].tobytes() == c[0].tobytes() and _stats_tuple(a[1]) == _stats_tuple(c[1])
+
+
+def test_buffers_are_reused_across_sizes():
+    used = R.Context(0)
+    _align(used, 20011, 19997, False)
+    ms, mt = _set_pair(used, 63, 65)
+    _check_eval(used, ms, mt, GC.pose2(), "eval (63,65) after (20011,19997)")
+    _check_cloud(used, 1, mt, "target 65 after 19997")
+    a = _align(used, 1999, 2113, False)
+    fresh = R.Context(0)
+    b = _align(fresh, 1999, 2113, False)
+    assert a[0].tobytes() == b[0].tobytes() and _stats_tuple(a[1]) == _stats_tuple(b[1])
+    used.close()
+    fresh.close()
+
+
+def test_two_contexts_on_two_threads(ctx):
+    ref = {k: _align(ctx, 1999, 2113, k) for k in (False, True)}
+    out, errs = {}, []
+
+    def work(k):
+        try:
+            c = R.Context(0)
+            for _ in range(2):
+                out[k] = _align(c, 1999, 2113, k)
+            c.close()
+        except Exception as e:   # noqa: BLE001
+            errs.append(e)
+
+    th = [threading.Thread(target=work, args=(k,)) for k in (False, True)]
+    [t.start() for t in th]
+    [t.join() for t in th]
+    assert not errs, errs
+    for k in (False, True):
+        assert out[k][0].tobytes() == ref[k][0].tobytes() and _stats_tuple(out[k][1]) == _stats_tuple(ref[k][1])
+
+
+def test_context_destroyed_and_created_again():
+    res = []
+    for _ in range(2):
+        c = R.Context(0)
+        res.append(_align(c, 1999, 2113, False))
+        c.close()
+    assert res[0][0].tobytes() == res[1][0].tobytes()
+
+
+def test_python_facade_gives_the_c_abi_result(ctx):
+    s, t = GC.pair(1999, 2113)
+    ref = _align(ctx, 1999, 2113, False)
+    g = R.GeneralizedICP(ctx)
+    g.setMaxCorrespondenceDistance(0.4)
+    g.setMaximumIterations(10)
+    g.setTransformationEpsilon(1e-9)
+    g.setRANSACOutlierRejectionThreshold(0.1)
+    g.setInputSource(s)
+    g.setInputTarget(t)
+    out = g.align()
+    T = g.getFinalTransformation()
+    assert T.tobytes() == ref[0].tobytes() and g.hasConverged() == bool(ref[1].converged)
+    assert g.getFitnessScore() == ref[1].fitness
+    assert out.shape == s.shape and np.abs(out - GC.transform(s, T.astype(np.float64))).max() <= 1e-5
+
+
+def _matrix_after(out, tag):
+    m = re.search(re.escape(tag) + r":?\s*\n((?:\s*\S+\s+\S+\s+\S+\s+\S+\s*\n){4})", out)
+    assert m, (tag, out[-2000:])
+    return np.array([float(x) for x in m.group(1).split()]).reshape(4, 4)
+
+
+def test_gicp_dropin_runs():
+    exe = os.path.join(ROOT, "build", "bin", "gicp_dropin")
+    assert os.path.exists(exe), f"{exe} missing: run __graft_entry__.build()"
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=100)
+    assert p.returncode == 0, p.stderr + p.stdout[-2000:]
+    T = _matrix_after(p.stdout, "ICP transformation")
+    assert np.isfinite(T).all(), p.stdout
+
+
+def test_register_pair_app_prints_both_transformations():
+    exe = os.path.join(ROOT, "build", "bin", "RegisterPairRGBD360")
+    assert os.path.exists(exe), f"{exe} missing: run __graft_entry__.build()"
+    p1, p2 = (os.path.join(R.SAMPLES_DIR, f"sphere_images_{i}.bin") for i in (1, 10))
+    p = subprocess.run([exe, p1, p2], capture_output=True, text=True, timeout=100)
+    assert p.returncode == 0, p.stderr + p.stdout[-2000:]
+    T = _matrix_after(p.stdout, "ICP transformation")
+    P = _matrix_after(p.stdout, "PbMap-Registration")
+    assert np.isfinite(T).all() and np.isfinite(P).all(), p.stdout
+    # recorded, not asserted: nothing pins what GICP should give on real data
+    print(f"GICP vs PbMap on the sample pair: {GM.rot_angle(T, P):.4g} rad, "
+          f"{np.linalg.norm(T[:3, 3] - P[:3, 3]):.4g} m")
