@@ -1,0 +1,272 @@
+// KFsphereSLAM — apps/KFsphereTracking.cpp's front end plus the back half of the reference's SLAM/KFsphere_SLAM.cpp,
+// written against the façade (include/rgbd360/rgbd360.h):
+//   * every new keyframe adds a vertex at the chained pose (:541) and the dense edge from the keyframe it was
+//     tracked against (:544: the dense pose and align360.getHessian(), unchanged), and the PbMap edge under the
+//     reference's test (:547-550: good tracking, at least 4 matched planes, more than 6 m2 matched, within 5 degrees
+//     and 0.1 m of the dense pose; registerer.getInfoMat());
+//   * the keyframe is then registered against the earlier keyframes within 5 m (LoopClosure360.h:294) that lie at
+//     least --min-gap keyframes back (default 3): RegisterPbMap, more than minMatchesThreshold = 5 matched planes and
+//     more than areaThreshold = 15 m2 (:114-115, :298), the dense refinement from the PbMap pose (:306-313) and
+//     avDepthResidual < 2.0 (:316; assigned only by the occlusion variants, so the test applies with occlusion 1 / 2);
+//     a loop edge carries the refined pose and align360.getHessian() (:318);
+//   * the graph is optimised whenever a loop edge was added (:679), the optimised poses replace the chain's
+//     (:689, :705) and tracking goes on from the optimised pose of the last keyframe.
+// At the end: the chained and the optimised keyframe poses, in synthetic mode each one's distance from the path
+// (r360_synth_path_pose), and the global map fused twice (r360_ctx_map_add_frame), at the chained and at the
+// optimised poses, with both sizes.
+//   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o]
+//          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
+//          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
+#include <rgbd360/rgbd360.h>
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <string>
+#include <sys/stat.h>
+#include <vector>
+
+static bool fexists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }
+
+typedef r360::Matrix4f Matrix4f;
+
+static float translationNorm(const Matrix4f& T) {
+    return std::sqrt(T(0, 3) * T(0, 3) + T(1, 3) * T(1, 3) + T(2, 3) * T(2, 3));
+}
+// Miscellaneous.h:127-149: the angle (degrees) and the distance between two poses
+static float diffRotation(const Matrix4f& a, const Matrix4f& b) {
+    float tr = 0.f;
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) tr += a(r, c) * b(r, c);
+    const float cs = std::fmax(-1.f, std::fmin(1.f, (tr - 1.f) / 2.f));
+    return std::acos(cs) * 180.f / 3.14159265359f;
+}
+static float difTranslation(const Matrix4f& a, const Matrix4f& b) { return translationNorm(a.inverse() * b); }
+
+int main(int argc, char** argv) {
+    std::vector<std::string> pos;
+    int min_gap = 3;
+    float kf_dist = 0.4f;
+    std::string save, frames_arg;
+    int n_synth = 0;
+    bool synthetic = false;
+    for (int k = 1; k < argc; ++k) {
+        const std::string a = argv[k];
+        if (a == "--min-gap" && k + 1 < argc) min_gap = std::atoi(argv[++k]);
+        else if (a == "--kf-dist" && k + 1 < argc) kf_dist = float(std::atof(argv[++k]));
+        else if (a == "--save" && k + 1 < argc) save = argv[++k];
+        else if (a == "--synthetic-frames" && k + 1 < argc) { frames_arg = argv[++k]; synthetic = true; }
+        else if (a == "--synthetic" && k + 1 < argc) { n_synth = std::atoi(argv[++k]); synthetic = true; }
+        else pos.push_back(a);
+    }
+    std::vector<int> order;                              // the frames to read, in order
+    for (size_t p = 0; p < frames_arg.size();) {
+        size_t q = frames_arg.find(',', p);
+        if (q == std::string::npos) q = frames_arg.size();
+        order.push_back(std::atoi(frames_arg.substr(p, q - p).c_str()));
+        p = q + 1;
+    }
+    for (int k = 0; k < n_synth && frames_arg.empty(); ++k) order.push_back(k);
+    if ((synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
+        std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
+                             "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o]\n", argv[0]);
+        return 1;
+    }
+    const std::string dir = synthetic ? "" : pos[0];
+    const int first = synthetic ? 0 : std::atoi(pos[1].c_str()), step = synthetic ? 1 : std::atoi(pos[2].c_str());
+    const size_t occ_at = synthetic ? 0 : 3;
+    const int occlusion = pos.size() > occ_at ? std::atoi(pos[occ_at].c_str()) : 1;
+    const float selectKF_ICPdist = 0.9f;                 // KFsphere_SLAM.cpp:388
+    const size_t minMatchesThreshold = 5;                // LoopClosure360.h:114-115
+    const float areaThreshold = 15.0f;
+    try {
+        r360::Context ctx(0);
+        r360::Calib360 calib(ctx, synthetic ? 480 : 240, synthetic ? 640 : 320);
+        calib.loadExtrinsicCalibration(std::string(RGBD360_DATA_DIR) + "/calib/Extrinsics");
+        if (!synthetic) calib.loadIntrinsicCalibration(std::string(RGBD360_DATA_DIR) + "/calib/Intrinsics");
+        r360::RegisterRGBD360 registerer(ctx, std::string(RGBD360_DATA_DIR) + "/config_files/configLocaliser_sphericalOdometry.ini");
+        r360::RegisterPhotoICP align360(ctx);
+        align360.setNumPyr(5);
+        align360.useSaliency(false);
+        align360.setVisualization(false);
+        align360.setGrayVariance(3.f / 255);
+        const float angleOffset = 157.5f;
+        Matrix4f rotOffset, rotOffsetInv;
+        rotOffset(1, 1) = rotOffset(2, 2) = std::cos(angleOffset * 3.14159265359 / 180);
+        rotOffset(1, 2) = std::sin(angleOffset * 3.14159265359 / 180);
+        rotOffset(2, 1) = -rotOffset(1, 2);
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) rotOffsetInv(r, c) = rotOffset(c, r);
+
+        const uint32_t seed = 360u << 16;
+        std::vector<uint8_t> bgr;
+        std::vector<uint16_t> depth;
+        // the n-th frame of the run; *id = its path index (synthetic) or file number
+        auto load = [&](r360::Frame360& f, size_t n, int* id) -> bool {
+            if (synthetic) {
+                if (n >= order.size()) return false;
+                *id = order[n];
+                float P[16];
+                r360_synth_path_pose(seed, *id, P);
+                bgr.resize(size_t(8) * 480 * 640 * 3);
+                depth.resize(size_t(8) * 480 * 640);
+                r360::check(r360_synth_frame(calib.get(), seed, P, bgr.data(), depth.data()), "synth_frame");
+                f.upload(bgr.data(), depth.data());
+                return true;
+            }
+            *id = first + int(n) * step;
+            const std::string path = dir + "/sphere_images_" + std::to_string(*id) + ".bin";
+            if (!fexists(path)) return false;
+            f.loadFrame(path);
+            return true;
+        };
+
+        // KFsphere_SLAM.cpp:263-265
+        r360::GraphOptimizer optimizer(ctx);
+        optimizer.setRigidTransformationType(r360::GraphOptimizer::SixDegreesOfFreedom);
+        std::vector<std::unique_ptr<r360::Frame360> > kfs;
+        std::vector<int> kfId;
+        std::vector<Matrix4f> chainPose;                 // the raw product of dense poses
+        std::vector<Matrix4f> vOptimizedPoses;           // Map.vOptimizedPoses: the chain until a loop closes
+        int id = 0;
+        kfs.emplace_back(new r360::Frame360(&calib));
+        if (!load(*kfs.back(), 0, &id)) { std::fprintf(stderr, "no first frame\n"); return 3; }
+        kfs.back()->getPlanes();
+        kfs.back()->stitchSphericalImage();
+        kfId.push_back(id);
+        Matrix4f currentPose = Matrix4f::Identity();
+        chainPose.push_back(currentPose);
+        vOptimizedPoses.push_back(currentPose);
+        std::printf("Added vertex: %d\n", optimizer.addVertex(currentPose.cast<double>()));
+        Matrix4f rigidTransf_dense_ref = Matrix4f::Identity();
+        int loops = 0, optimisations = 0;
+        double F_first = 0.0, F_last = 0.0;
+        for (size_t n = 1;; ++n) {
+            std::unique_ptr<r360::Frame360> frame(new r360::Frame360(&calib));
+            if (!load(*frame, n, &id)) break;
+            frame->getPlanes();
+            frame->stitchSphericalImage();
+            r360::Frame360* kf = kfs.back().get();
+            const int nearestKF = int(kfs.size()) - 1;
+            const bool bGoodTracking = registerer.RegisterPbMap(kf, frame.get(), 25, r360::RegisterRGBD360::PLANAR_3DoF);
+            Matrix4f trackedPosePbMap = registerer.getPose();
+            const size_t trackedMatches = registerer.getMatchedPlanes().size();
+            const float trackedArea = registerer.getAreaMatched();
+            const r360::Matrix6f trackedInfo = bGoodTracking ? registerer.getInfoMat() : r360::Matrix6f::Identity();
+            if (bGoodTracking) rigidTransf_dense_ref = rotOffset * trackedPosePbMap * rotOffsetInv;
+            align360.setTargetFrame(kf->sphereRGB, kf->sphereDepth);
+            align360.setSourceFrame(frame->sphereRGB, frame->sphereDepth);
+            const bool ok = align360.alignFrames360(rigidTransf_dense_ref, r360::RegisterPhotoICP::PHOTO_DEPTH, occlusion);
+            rigidTransf_dense_ref = align360.getOptimalPose();
+            Matrix4f rigidTransf_dense = rotOffsetInv * rigidTransf_dense_ref * rotOffset;
+            const r360::Matrix6f hessian = align360.getHessian();
+            const float dist = translationNorm(rigidTransf_dense);
+            std::printf("frame %d: PbMap %s matches %zu area %.3f; dense %s dist %.3f residuals %.5f %.5f\n", id,
+                        bGoodTracking ? "ok" : "failed", trackedMatches, trackedArea, ok ? "ok" : "ILL-POSED", dist,
+                        align360.avPhotoResidual, align360.avDepthResidual);
+            const bool far = dist > kf_dist || (occlusion && !(align360.avDepthResidual < selectKF_ICPdist));
+            if (!far || !ok) continue;
+
+            // a new keyframe (:536-550)
+            chainPose.push_back(chainPose.back() * rigidTransf_dense);
+            currentPose = currentPose * rigidTransf_dense;
+            const int newFrameID = optimizer.addVertex(currentPose.cast<double>());
+            std::printf("Added vertex: %d (frame %d)\n", newFrameID, id);
+            optimizer.addEdge(nearestKF, newFrameID, rigidTransf_dense.cast<double>(), hessian.cast<double>());
+            if (bGoodTracking && trackedMatches >= 4 && trackedArea > 6)
+                if (diffRotation(trackedPosePbMap, rigidTransf_dense) < 5 && difTranslation(trackedPosePbMap, rigidTransf_dense) < 0.1) {
+                    optimizer.addEdge(nearestKF, newFrameID, trackedPosePbMap.cast<double>(), trackedInfo.cast<double>());
+                    std::printf("Added addEdge PbMap %d %d\n", nearestKF, newFrameID);
+                }
+            kfs.push_back(std::move(frame));
+            kfId.push_back(id);
+            vOptimizedPoses.push_back(currentPose);
+            rigidTransf_dense_ref = Matrix4f::Identity();
+            r360::Frame360* newKF = kfs.back().get();
+
+            // loop closure against the earlier keyframes (LoopClosure360.h:290-321)
+            bool bHasNewLC = false;
+            for (int compareLocalIdx = 0; compareLocalIdx + min_gap <= newFrameID; ++compareLocalIdx) {
+                Matrix4f relativePose = vOptimizedPoses[compareLocalIdx].inverse() * currentPose;
+                const float distance = translationNorm(relativePose);
+                if (!(distance < 5.f)) continue;
+                const bool bGoodRegistration =
+                    registerer.RegisterPbMap(kfs[compareLocalIdx].get(), newKF, 25, r360::RegisterRGBD360::PLANAR_3DoF);
+                std::printf("Check loop closure between %d and %d: %s matches %zu area %.3f\n", newFrameID, compareLocalIdx,
+                            bGoodRegistration ? "ok" : "failed", registerer.getMatchedPlanes().size(), registerer.getAreaMatched());
+                if (!(bGoodRegistration && registerer.getMatchedPlanes().size() > minMatchesThreshold &&
+                      registerer.getAreaMatched() > areaThreshold))
+                    continue;
+                relativePose = registerer.getPose();
+                align360.setTargetFrame(kfs[compareLocalIdx]->sphereRGB, kfs[compareLocalIdx]->sphereDepth);
+                align360.setSourceFrame(newKF->sphereRGB, newKF->sphereDepth);
+                const Matrix4f initTransf_dense = rotOffset * relativePose * rotOffsetInv;
+                const bool lok = align360.alignFrames360(initTransf_dense, r360::RegisterPhotoICP::PHOTO_DEPTH, occlusion);
+                relativePose = rotOffsetInv * align360.getOptimalPose() * rotOffset;
+                const r360::Matrix6f informationMatrix = align360.getHessian();
+                if (lok && (!occlusion || align360.avDepthResidual < 2.0)) {
+                    optimizer.addEdge(compareLocalIdx, newFrameID, relativePose.cast<double>(), informationMatrix.cast<double>());
+                    std::printf("LC Add edge between %d and %d (residual %.5f)\n", compareLocalIdx, newFrameID, align360.avDepthResidual);
+                    bHasNewLC = true;
+                    ++loops;
+                }
+            }
+            if (bHasNewLC) {                             // :679-705
+                optimizer.optimizeGraph();
+                optimizer.getPoses(vOptimizedPoses);
+                currentPose = vOptimizedPoses.back();
+                const r360_graph_stats& st = optimizer.stats();
+                if (optimisations++ == 0) F_first = st.F_initial;
+                F_last = st.F_final;
+                std::printf("Optimize graph SLAM %zu: status %d iterations %d cost %.9g -> %.9g\n", kfs.size(), st.status, st.iterations,
+                            st.F_initial, st.F_final);
+            }
+        }
+
+        std::printf("%zu keyframes, %d loop edges, %d optimisations", kfs.size(), loops, optimisations);
+        if (optimisations) std::printf(", cost %.9g -> %.9g", F_first, F_last);
+        std::printf("\n");
+        Matrix4f P0inv = Matrix4f::Identity();
+        if (synthetic) {
+            Matrix4f P0;
+            r360_synth_path_pose(seed, kfId[0], P0.data());
+            P0inv = P0.inverse();
+        }
+        double worstChain = 0, worstOpt = 0;
+        for (size_t k = 0; k < kfs.size(); ++k) {
+            const Matrix4f& C = chainPose[k];
+            const Matrix4f& O = vOptimizedPoses[k];
+            std::printf("keyframe %zu frame %d chain %.9g %.9g %.9g optimised %.9g %.9g %.9g", k, kfId[k], C(0, 3), C(1, 3), C(2, 3),
+                        O(0, 3), O(1, 3), O(2, 3));
+            if (synthetic) {
+                Matrix4f P;
+                r360_synth_path_pose(seed, kfId[k], P.data());
+                const Matrix4f truth = P0inv * P;
+                const float dc = difTranslation(truth, C), dopt = difTranslation(truth, O);
+                worstChain = std::fmax(worstChain, dc);
+                worstOpt = std::fmax(worstOpt, dopt);
+                std::printf(" from path %.4f %.4f", dc, dopt);
+            }
+            bool same = true;
+            for (int e = 0; e < 16; ++e) same = same && C.data()[e] == O.data()[e];
+            std::printf(" %s\n", same ? "same" : "moved");
+        }
+        if (synthetic) std::printf("worst distance from the path: chain %.4f m, optimised %.4f m\n", worstChain, worstOpt);
+
+        // the global map, fused at the chained and at the optimised poses
+        r360::GlobalMap360 map(ctx, 0.05f, 4.0f);
+        size_t sizes[2] = {0, 0};
+        for (int which = 0; which < 2; ++which) {
+            map.reset();
+            for (size_t k = 0; k < kfs.size(); ++k) map.add(*kfs[k], which ? vOptimizedPoses[k] : chainPose[k]);
+            sizes[which] = map.size();
+        }
+        std::printf("global map: %zu points at the chained poses, %zu at the optimised poses\n", sizes[0], sizes[1]);
+        if (!save.empty()) optimizer.saveGraph(save);
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "error: %s\n", e.what());
+        return 2;
+    }
+    return 0;
+}

@@ -15,7 +15,8 @@
 //
 // What it provides, all opt-in through this header only:
 //   * Calib360, Frame360, RegisterPhotoICP, RegisterRGBD360, Plane in the global namespace;
-//   * Eigen::Matrix4f and Eigen::Matrix<float,6,6> as r360::Matrix4f / Matrix6f when Eigen itself is not used
+//   * Eigen::Matrix4f and Eigen::Matrix<float,6,6> as r360::Matrix4f / Matrix6f when Eigen itself is not used, with
+//     cast<double>() into the Eigen::Matrix4d / Matrix<double,6,6> stand-ins GraphOptimizer takes
 //     (RGBD360_WITH_EIGEN makes the façade use the real Eigen types instead);
 //   * mrpt::format (printf-style std::string) unless MRPT's own header came first;
 //   * PROJECT_SOURCE_PATH = r360_data_dir() (data/) unless the build defines it, so the reference's
@@ -25,12 +26,14 @@
 #include <rgbd360/rgbd360.h>
 
 #include <fstream>
+#include <memory>
 #include <string>
 
 using r360::Calib360;
 using r360::FilterPointCloud;
 using r360::GeneralizedIterativeClosestPoint;
 using r360::Frame360;
+using r360::GraphOptimizer;
 using r360::PbMap;
 using r360::Plane;
 using r360::RegisterPhotoICP;
@@ -42,9 +45,15 @@ template <typename Scalar, int Rows, int Cols>
 struct EigenStandIn;                    // only the two fixed-size float matrices of the registration surface
 template <> struct EigenStandIn<float, 4, 4> { typedef Matrix4f type; };
 template <> struct EigenStandIn<float, 6, 6> { typedef Matrix6f type; };
+template <> struct EigenStandIn<double, 4, 4> { typedef Matrix4d type; };   // GraphOptimizer's arguments
+template <> struct EigenStandIn<double, 6, 6> { typedef Matrix6d type; };
 }  // namespace r360
 namespace Eigen {
 typedef r360::Matrix4f Matrix4f;
+typedef r360::Matrix4d Matrix4d;
+// std::vector<Eigen::Matrix4f, Eigen::aligned_allocator<Eigen::Matrix4f> > (Map.vOptimizedPoses, GraphOptimizer::getPoses)
+template <class T>
+using aligned_allocator = std::allocator<T>;
 // Eigen::Matrix<float,6,6> (getInfoMat / getHessian, SphereGraphSLAM.cpp:200-201, LoopClosure360.h:314) and
 // Eigen::Matrix<float,4,4>
 template <typename Scalar, int Rows, int Cols, int Options = 0, int MaxRows = Rows, int MaxCols = Cols>

@@ -63,10 +63,21 @@ inline int check(int rc, const char* what) {
 #ifdef RGBD360_WITH_EIGEN
 typedef Eigen::Matrix4f Matrix4f;
 typedef Eigen::Matrix<float, 6, 6> Matrix6f;
+typedef Eigen::Matrix4d Matrix4d;
+typedef Eigen::Matrix<double, 6, 6> Matrix6d;
 #else
+template <typename T, int N>
+struct MatrixOf;                        // the stand-in of Eigen::Matrix<T, N, N>: what cast<T>() returns
 template <int N>
 struct MatrixNf {                       // column-major, Eigen's (row, col) and data()
     float v[N * N];
+    // currentPose.cast<double>() (KFsphere_SLAM.cpp:265, 541-550; LoopClosure360.h:318)
+    template <typename T>
+    typename MatrixOf<T, N>::type cast() const {
+        typename MatrixOf<T, N>::type o;
+        for (int i = 0; i < N * N; ++i) o.v[i] = T(v[i]);
+        return o;
+    }
     MatrixNf() { for (int i = 0; i < N * N; ++i) v[i] = (i % (N + 1) == 0) ? 1.f : 0.f; }
     static MatrixNf Identity() { return MatrixNf(); }
     float& operator()(int r, int c) { return v[c * N + r]; }
@@ -133,8 +144,37 @@ inline MatrixNf<N> operator*(float s, const MatrixNf<N>& m) {
     for (int i = 0; i < N * N; ++i) o.v[i] = s * m.v[i];
     return o;
 }
+// Eigen::Matrix<double, N, N> as the graph optimiser takes it: storage, (row, col), data() and cast
+template <int N>
+struct MatrixNd {
+    double v[N * N];
+    MatrixNd() { for (int i = 0; i < N * N; ++i) v[i] = (i % (N + 1) == 0) ? 1.0 : 0.0; }
+    static MatrixNd Identity() { return MatrixNd(); }
+    double& operator()(int r, int c) { return v[c * N + r]; }
+    double operator()(int r, int c) const { return v[c * N + r]; }
+    double* data() { return v; }
+    const double* data() const { return v; }
+    template <typename T>
+    typename MatrixOf<T, N>::type cast() const {
+        typename MatrixOf<T, N>::type o;
+        for (int i = 0; i < N * N; ++i) o.v[i] = T(v[i]);
+        return o;
+    }
+};
+template <int N>
+inline std::ostream& operator<<(std::ostream& os, const MatrixNd<N>& m) {
+    for (int r = 0; r < N; ++r) {
+        for (int c = 0; c < N; ++c) os << (c ? " " : "") << m(r, c);
+        if (r + 1 < N) os << "\n";
+    }
+    return os;
+}
+template <int N> struct MatrixOf<float, N> { typedef MatrixNf<N> type; };
+template <int N> struct MatrixOf<double, N> { typedef MatrixNd<N> type; };
 typedef MatrixNf<4> Matrix4f;
 typedef MatrixNf<6> Matrix6f;
+typedef MatrixNd<4> Matrix4d;
+typedef MatrixNd<6> Matrix6d;
 #endif
 
 class Frame360;
@@ -849,6 +889,65 @@ class GeneralizedIterativeClosestPoint {
     Matrix4f T_ = Matrix4f::Identity();
     double ransac_ = 0.05;
     bool illposed_ = false;
+};
+
+// ------------------------------------------------------------------ GraphOptimizer
+// include/GraphOptimizer.h with its members and signatures, over r360_graph_* (the g2o Levenberg-Marquardt restated,
+// its linear solve a block-sparse conjugate gradient on the GPU: DESIGN.md §5d).  The default constructor gives the
+// optimiser a context of its own, so an optimiser built on one thread and used on another (LoopClosure360's member,
+// LoopClosure360.h:58, 89-91) shares no stream with either.  ThreeDegreesOfFreedom throws: the reference's own 3-DoF
+// addVertex and addEdge bodies are commented out.
+class GraphOptimizer {
+  public:
+    enum RigidTransformationType { SixDegreesOfFreedom = 0, ThreeDegreesOfFreedom = 1 } rigidTransformationType;
+    int vertex_id = 0;                  // the index of the next vertex (the graph's size)
+    r360_graph_params params;           // max_iterations = 10 is the reference's optimize(10)
+    GraphOptimizer() : keep_(std::make_shared<Context>(default_device())), ctx_(keep_.get()) { init(); }
+    explicit GraphOptimizer(Context& ctx) : ctx_(&ctx) { init(); }
+    ~GraphOptimizer() { r360_graph_destroy(h_); }
+    GraphOptimizer(const GraphOptimizer&) = delete;
+    GraphOptimizer& operator=(const GraphOptimizer&) = delete;
+    int addVertex(const Matrix4d vertexPose) {
+        int id = -1;
+        check(r360_graph_add_vertex(h_, vertexPose.data(), &id), "GraphOptimizer::addVertex");
+        vertex_id = id + 1;
+        return id;
+    }
+    void addEdge(const int fromIdx, const int toIdx, const Matrix4d relativePose, const Matrix6d informationMatrix) {
+        check(r360_graph_add_edge(h_, fromIdx, toIdx, relativePose.data(), informationMatrix.data()), "GraphOptimizer::addEdge");
+    }
+    void optimizeGraph() { check(r360_graph_optimize(h_, &params, &stats_), "GraphOptimizer::optimizeGraph"); }
+    template <class Alloc>
+    void getPoses(std::vector<Matrix4f, Alloc>& poses) {
+        int n = 0;
+        check(r360_graph_get_poses(h_, nullptr, 0, &n), "GraphOptimizer::getPoses");
+        std::vector<double> p(16 * size_t(n));
+        check(r360_graph_get_poses(h_, p.data(), n, &n), "GraphOptimizer::getPoses");
+        poses.clear();
+        poses.resize(n);
+        for (int k = 0; k < n; ++k)
+            for (int c = 0; c < 4; ++c)
+                for (int r = 0; r < 4; ++r) poses[k](r, c) = float(p[16 * size_t(k) + c * 4 + r]);
+    }
+    void saveGraph(std::string fileName) { check(r360_graph_save(h_, fileName.c_str()), "GraphOptimizer::saveGraph"); }
+    void setFixed(int idx, bool fixed) { check(r360_graph_set_fixed(h_, idx, fixed ? 1 : 0), "GraphOptimizer::setFixed"); }
+    inline void setRigidTransformationType(RigidTransformationType rttype) {
+        if (rttype != SixDegreesOfFreedom)
+            throw std::invalid_argument("GraphOptimizer: ThreeDegreesOfFreedom is not supported (the reference's 3-DoF bodies are commented out)");
+        rigidTransformationType = rttype;
+    }
+    const r360_graph_stats& stats() const { return stats_; }
+    r360_graph* get() const { return h_; }
+  private:
+    void init() {
+        rigidTransformationType = SixDegreesOfFreedom;
+        r360_graph_default_params(&params);
+        check(r360_graph_create(ctx_->get(), &h_), "r360_graph_create");
+    }
+    std::shared_ptr<Context> keep_;     // declared before h_: the graph goes first, then its context
+    Context* ctx_;
+    r360_graph* h_ = nullptr;
+    r360_graph_stats stats_ = r360_graph_stats();
 };
 
 }  // namespace r360

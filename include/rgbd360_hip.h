@@ -747,6 +747,81 @@ int r360_gicp_get_cloud(r360_ctx* ctx, int which, float* xyz, float* cov6, int* 
 int r360_gicp_eval(r360_ctx* ctx, const float pose[16], const r360_gicp_params* p, int* corr, double* cost,
                    double H[36], double g[6], size_t* n_corr);
 
+/* ---------------------------------------------------------------- pose-graph optimisation
+ * include/GraphOptimizer.h (g2o VertexSE3 / EdgeSE3, OptimizationAlgorithmLevenberg over LinearSolverDense,
+ * optimize(10)) restated (g2o is not pinned): the statement is tests/pgo_model.py and DESIGN.md §5d.  A vertex is a
+ * pose, world from keyframe; an edge (from, to, rel, info) says T_to ~ T_from * rel, with info the 6x6 information
+ * matrix ordered (translation, rotation), symmetrised on intake and otherwise used as given (getHessian() and
+ * getInfoMat() go in unchanged, as in the reference).  Poses and information matrices are COLUMN-major double (the
+ * reference casts to double at every call).  Vertex 0 is always fixed (GraphOptimizer.h:105-106).
+ * The residual of an edge is e = [t_E ; log(R_E)] of E = rel^-1 T_from^-1 T_to, the cost F = sum e^T info e, the
+ * increment T * [Exp(d_w), d_t]; Levenberg-Marquardt after g2o's scheme runs on the host, every sum, the block-sparse
+ * H and the block-Jacobi-preconditioned conjugate-gradient solve on the context's GPU, all in a fixed order: two runs
+ * give the same bytes.
+ * A graph is a handle of its own, as the reference's optimisers are objects (KFsphere_SLAM.cpp:263,
+ * LoopClosure360.h:58); it runs on its context's stream and the context must outlive it.
+ * R360_EINVAL: an argument or the graph fails a check (message in r360_last_error()); the handle stays usable. */
+#define R360_EINVAL (-2)
+typedef struct r360_graph r360_graph;
+typedef struct {
+    int max_iterations;      /* 10: the reference's optimize(10) */
+    int max_trials;          /* 10 damping trials per iteration */
+    double gain_epsilon;     /* 1e-6: stop when F - F' <= gain_epsilon F */
+    double cg_tolerance;     /* 1e-12: the recursive residual against |b| */
+    int cg_max_iterations;   /* 0: 12 * the number of free vertices */
+    int cg_form;             /* 0 automatic, 1 one workgroup (unknowns and CG vectors in LDS), 2 one launch per step */
+} r360_graph_params;
+enum { R360_GRAPH_CONVERGED = 0, R360_GRAPH_ITERATION_LIMIT = 1, R360_GRAPH_STALLED = 2, R360_GRAPH_CG_NOT_CONVERGED = 3 };
+typedef struct {
+    int status;                  /* R360_GRAPH_* */
+    int iterations, trials;      /* accepted outer iterations, damped solves in all */
+    int cg_form;                 /* the form that ran (1 or 2; 0 if no solve ran) */
+    double F_initial, F_final, lambda;
+    long long cg_iterations;     /* in all */
+    int cg_iterations_max;       /* of one solve */
+    int pad;
+} r360_graph_stats;
+int  r360_graph_create(r360_ctx* ctx, r360_graph** out);
+void r360_graph_destroy(r360_graph* g);
+/* addVertex (GraphOptimizer.h:96-110; KFsphere_SLAM.cpp:265, 541): *id = the new vertex's index. */
+int  r360_graph_add_vertex(r360_graph* g, const double pose[16], int* id);
+/* setFixed of a vertex (KFsphere_SLAM.cpp:668-676); vertex 0 cannot be freed. */
+int  r360_graph_set_fixed(r360_graph* g, int id, int fixed);
+int  r360_graph_set_pose(r360_graph* g, int id, const double pose[16]);
+/* addEdge(from, to, relativePose, information) (GraphOptimizer.h:113-133; KFsphere_SLAM.cpp:544, 550, 630;
+ * LoopClosure360.h:318).  Either index order; several edges of one pair add up. */
+int  r360_graph_add_edge(r360_graph* g, int from, int to, const double rel[16], const double info[36]);
+int  r360_graph_size(const r360_graph* g, int* n_vertices, int* n_edges);
+/* getPoses (GraphOptimizer.h:160-175): poses [cap][16]; *n is set either way, cap < *n with poses given is an error. */
+int  r360_graph_get_poses(const r360_graph* g, double* poses, int cap, int* n);
+void r360_graph_default_params(r360_graph_params* p);
+/* optimizeGraph (GraphOptimizer.h:137-157; KFsphere_SLAM.cpp:679-705).  params NULL = the defaults.  Returns 0 with
+ * stats->status set, R360_EINVAL when a free vertex has no edge, a connected component has no fixed vertex, or
+ * cg_form 1 is asked for a graph too large for it.  With status R360_GRAPH_CG_NOT_CONVERGED or R360_GRAPH_STALLED
+ * the poses are those of the last accepted iteration. */
+int  r360_graph_optimize(r360_graph* g, const r360_graph_params* params, r360_graph_stats* stats);
+/* Parity hooks (at most 1024 vertices).  The unknowns are the free vertices in index order, 6 each (translation,
+ * rotation).  eval: F, b [6 n_free] and H densified row-major [6 n_free][6 n_free] on the host from the device's
+ * blocks, at the current poses; *n_unknowns is set either way; cap = room in unknowns; b and H may be NULL.
+ * solve: one damped solve (H + lambda I) delta = -b with params' CG settings; returns 1 when CG ran out of
+ * iterations; *rel_residual = the recursive residual against |b|. */
+int  r360_graph_eval(r360_graph* g, double* F, double* b, double* H, int cap, int* n_unknowns);
+int  r360_graph_solve(r360_graph* g, const r360_graph_params* params, double lambda, double* delta, int cap,
+                      int* n_unknowns, int* iterations, double* rel_residual, int* form);
+/* g2o text files as saveGraph writes them (GraphOptimizer.h:178-181; KFsphere_SLAM.cpp:689): host only, no context.
+ *   VERTEX_SE3:QUAT id x y z qx qy qz qw  /  FIX id  /  EDGE_SE3:QUAT i j x y z qx qy qz qw + the 21 upper-triangular
+ * entries of info, row-major; %.17g; Shepperd's quaternion with qw >= 0, snapped to a 2^-48 lattice of directions so
+ * that read-then-write reproduces the file byte for byte (a rotation entry moves by < 1e-14).
+ * write: poses [n][16], fixed [n] (may be NULL), ij [m][2], rel [m][16], info [m][36].  read: any output may be NULL;
+ * the counts are set either way; all outputs NULL = only count and check.  A malformed file is R360_EINVAL. */
+int  r360_g2o_write(const char* path, int n_vertices, const double* poses, const int* fixed, int n_edges, const int* ij,
+                    const double* rel, const double* info);
+int  r360_g2o_read(const char* path, double* poses, int* fixed, int cap_vertices, int* n_vertices, int* ij, double* rel,
+                   double* info, int cap_edges, int* n_edges);
+/* saveGraph / the matching load: load replaces the graph's vertices and edges. */
+int  r360_graph_save(const r360_graph* g, const char* path);
+int  r360_graph_load(r360_graph* g, const char* path);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ C = C  # re-exported for callers that drive the C-ABI directly (bench.py)
 
 __all__ = [
     "lib", "Context", "Calib360", "Frame360", "RegisterPhotoICP", "RegisterRGBD360", "IcpParams", "IcpStats",
-    "GicpParams", "GicpStats", "GeneralizedICP",
+    "GicpParams", "GicpStats", "GeneralizedICP", "GraphParams", "GraphStats", "PoseGraph", "g2o_write", "g2o_read",
     "PHOTO_CONSISTENCY", "DEPTH_CONSISTENCY", "PHOTO_DEPTH", "synth_path_pose", "exp_se3",
     "LIB_PATH", "ABI_SYMBOLS", "Batch", "PairJob", "PairResult", "JOB_PBMAP_ONLY", "JOB_GATED", "JOB_ALWAYS",
 ]
@@ -78,6 +78,34 @@ class GicpStats(C.Structure):
         ("iterations", C.c_int), ("converged", C.c_int), ("inner_steps", C.c_int), ("n_corr", C.c_size_t),
         ("cost", C.c_double), ("fitness", C.c_double),
     ]
+
+
+class GraphParams(C.Structure):
+    """r360_graph_params — pose-graph optimisation settings (see include/rgbd360_hip.h)."""
+    _fields_ = [
+        ("max_iterations", C.c_int), ("max_trials", C.c_int), ("gain_epsilon", C.c_double), ("cg_tolerance", C.c_double),
+        ("cg_max_iterations", C.c_int), ("cg_form", C.c_int),
+    ]
+
+    @classmethod
+    def default(cls, **kw) -> "GraphParams":
+        p = cls()
+        lib().r360_graph_default_params(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+
+class GraphStats(C.Structure):
+    """r360_graph_stats — what one r360_graph_optimize did."""
+    _fields_ = [
+        ("status", C.c_int), ("iterations", C.c_int), ("trials", C.c_int), ("cg_form", C.c_int),
+        ("F_initial", C.c_double), ("F_final", C.c_double), ("lambda_", C.c_double), ("cg_iterations", C.c_longlong),
+        ("cg_iterations_max", C.c_int), ("pad", C.c_int),
+    ]
+
+
+GRAPH_CONVERGED, GRAPH_ITERATION_LIMIT, GRAPH_STALLED, GRAPH_CG_NOT_CONVERGED = 0, 1, 2, 3
 
 
 class MatchParams(C.Structure):
@@ -334,6 +362,22 @@ _SIGS = [
     ("r360_gicp_align", C.c_int, [_P, _FP, C.POINTER(GicpParams), _FP, C.POINTER(GicpStats)]),
     ("r360_gicp_get_cloud", C.c_int, [_P, C.c_int, _FP, _FP, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r360_gicp_eval", C.c_int, [_P, _FP, C.POINTER(GicpParams), _IP, _DP, _DP, _DP, C.POINTER(C.c_size_t)]),
+    ("r360_graph_create", C.c_int, [_P, C.POINTER(_P)]),
+    ("r360_graph_destroy", None, [_P]),
+    ("r360_graph_add_vertex", C.c_int, [_P, _DP, _IP]),
+    ("r360_graph_set_fixed", C.c_int, [_P, C.c_int, C.c_int]),
+    ("r360_graph_set_pose", C.c_int, [_P, C.c_int, _DP]),
+    ("r360_graph_add_edge", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
+    ("r360_graph_size", C.c_int, [_P, _IP, _IP]),
+    ("r360_graph_get_poses", C.c_int, [_P, _DP, C.c_int, _IP]),
+    ("r360_graph_default_params", None, [C.POINTER(GraphParams)]),
+    ("r360_graph_optimize", C.c_int, [_P, C.POINTER(GraphParams), C.POINTER(GraphStats)]),
+    ("r360_graph_eval", C.c_int, [_P, _DP, _DP, _DP, C.c_int, _IP]),
+    ("r360_graph_solve", C.c_int, [_P, C.POINTER(GraphParams), C.c_double, _DP, C.c_int, _IP, _IP, _DP, _IP]),
+    ("r360_g2o_write", C.c_int, [C.c_char_p, C.c_int, _DP, _IP, C.c_int, _IP, _DP, _DP]),
+    ("r360_g2o_read", C.c_int, [C.c_char_p, _DP, _IP, C.c_int, _IP, _IP, _DP, _DP, C.c_int, _IP]),
+    ("r360_graph_save", C.c_int, [_P, C.c_char_p]),
+    ("r360_graph_load", C.c_int, [_P, C.c_char_p]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -1611,3 +1655,126 @@ class GeneralizedICP:
     def getFinalTransformation(self) -> np.ndarray: return self._pose.copy()
     def hasConverged(self) -> bool: return bool(self.stats.converged)
     def getFitnessScore(self) -> float: return self.stats.fitness
+
+
+def _mat16d(m) -> np.ndarray:
+    """4x4 -> column-major double[16] (Eigen::Matrix4d::data())."""
+    return np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(4, 4).T).reshape(16).copy()
+
+
+def _mat36d(m) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(m, dtype=np.float64).reshape(6, 6).T).reshape(36).copy()
+
+
+def g2o_write(path: str, poses, fixed, edges):
+    """r360_g2o_write: poses [n] 4x4, fixed [n] flags (or None), edges [(i, j, rel 4x4, info 6x6)]."""
+    P = np.concatenate([_mat16d(T) for T in poses]) if len(poses) else np.zeros(0)
+    fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, dtype=np.int32))
+    ij = np.ascontiguousarray(np.array([[e[0], e[1]] for e in edges], dtype=np.int32).reshape(-1))
+    Z = np.concatenate([_mat16d(e[2]) for e in edges]) if len(edges) else np.zeros(0)
+    Om = np.concatenate([_mat36d(e[3]) for e in edges]) if len(edges) else np.zeros(0)
+    _check(lib().r360_g2o_write(path.encode(), len(poses), _dptr(P), None if fx is None else fx.ctypes.data_as(_IP),
+                                len(edges), ij.ctypes.data_as(_IP), _dptr(Z), _dptr(Om)), "g2o_write")
+
+
+def g2o_read(path: str):
+    """r360_g2o_read: (poses [n,4,4], fixed [n] int32, edges [(i, j, rel 4x4, info 6x6)])."""
+    nv, ne = C.c_int(), C.c_int()
+    _check(lib().r360_g2o_read(path.encode(), None, None, 0, C.byref(nv), None, None, None, 0, C.byref(ne)), "g2o_read")
+    P = np.zeros(16 * nv.value)
+    fx = np.zeros(nv.value, np.int32)
+    ij = np.zeros(2 * ne.value, np.int32)
+    Z = np.zeros(16 * ne.value)
+    Om = np.zeros(36 * ne.value)
+    _check(lib().r360_g2o_read(path.encode(), _dptr(P), fx.ctypes.data_as(_IP), nv.value, C.byref(nv),
+                               ij.ctypes.data_as(_IP), _dptr(Z), _dptr(Om), ne.value, C.byref(ne)), "g2o_read")
+    poses = P.reshape(-1, 4, 4).transpose(0, 2, 1).copy()
+    edges = [(int(ij[2 * e]), int(ij[2 * e + 1]), Z[16 * e:16 * e + 16].reshape(4, 4).T.copy(),
+              Om[36 * e:36 * e + 36].reshape(6, 6).T.copy()) for e in range(ne.value)]
+    return poses, fx, edges
+
+
+class PoseGraph:
+    """The reference's GraphOptimizer (include/GraphOptimizer.h) over r360_graph_*: addVertex / addEdge / optimizeGraph /
+    getPoses / saveGraph, on the context's GPU.  Poses are 4x4 float64, world from keyframe; an edge says
+    T_to ~ T_from @ rel with a 6x6 information matrix ordered (translation, rotation).  The context must stay open
+    while the graph is used; closing the graph after its context is safe."""
+
+    def __init__(self, ctx: "Context"):
+        h = C.c_void_p()
+        _check(lib().r360_graph_create(ctx.h, C.byref(h)), "r360_graph_create")
+        self.h, self.ctx = h, ctx
+        self.params = GraphParams.default()
+        self.stats = GraphStats()
+
+    def close(self):
+        if self.h:
+            lib().r360_graph_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def addVertex(self, pose) -> int:
+        i = C.c_int()
+        _check(lib().r360_graph_add_vertex(self.h, _dptr(_mat16d(pose)), C.byref(i)), "graph_add_vertex")
+        return i.value
+
+    def addEdge(self, i: int, j: int, rel, info):
+        _check(lib().r360_graph_add_edge(self.h, i, j, _dptr(_mat16d(rel)), _dptr(_mat36d(info))), "graph_add_edge")
+
+    def setFixed(self, i: int, fixed: bool = True):
+        _check(lib().r360_graph_set_fixed(self.h, i, int(fixed)), "graph_set_fixed")
+
+    def setPose(self, i: int, pose):
+        _check(lib().r360_graph_set_pose(self.h, i, _dptr(_mat16d(pose))), "graph_set_pose")
+
+    def size(self):
+        nv, ne = C.c_int(), C.c_int()
+        _check(lib().r360_graph_size(self.h, C.byref(nv), C.byref(ne)), "graph_size")
+        return nv.value, ne.value
+
+    def getPoses(self) -> np.ndarray:
+        n = self.size()[0]
+        P = np.zeros(16 * n)
+        m = C.c_int()
+        _check(lib().r360_graph_get_poses(self.h, _dptr(P), n, C.byref(m)), "graph_get_poses")
+        return P.reshape(n, 4, 4).transpose(0, 2, 1).copy()
+
+    def optimizeGraph(self, params: "GraphParams | None" = None) -> "GraphStats":
+        st = GraphStats()
+        p = params if params is not None else self.params
+        _check(lib().r360_graph_optimize(self.h, C.byref(p), C.byref(st)), "graph_optimize")
+        self.stats = st
+        return st
+
+    def eval(self):
+        """r360_graph_eval: (F, b [N], H [N, N]) over the free vertices in index order."""
+        n = C.c_int()
+        _check(lib().r360_graph_eval(self.h, None, None, None, 0, C.byref(n)), "graph_eval")
+        N = n.value
+        F = C.c_double()
+        b = np.zeros(max(N, 1))
+        H = np.zeros((max(N, 1), max(N, 1)))
+        _check(lib().r360_graph_eval(self.h, C.byref(F), _dptr(b), _dptr(H), N, C.byref(n)), "graph_eval")
+        return F.value, b[:N].copy(), H[:N, :N].copy() if N else np.zeros((0, 0))
+
+    def solve(self, lam: float, params: "GraphParams | None" = None):
+        """r360_graph_solve: (delta [N], iterations, relative residual, form, converged)."""
+        n = C.c_int()
+        p = params if params is not None else self.params
+        _check(lib().r360_graph_solve(self.h, C.byref(p), lam, None, 0, C.byref(n), None, None, None), "graph_solve")
+        d = np.zeros(n.value)
+        it, form, rel = C.c_int(), C.c_int(), C.c_double()
+        rc = _check(lib().r360_graph_solve(self.h, C.byref(p), lam, _dptr(d), n.value, C.byref(n), C.byref(it),
+                                           C.byref(rel), C.byref(form)), "graph_solve")
+        return d, it.value, rel.value, form.value, rc == 0
+
+    def saveGraph(self, path: str):
+        _check(lib().r360_graph_save(self.h, path.encode()), "graph_save")
+
+    def loadGraph(self, path: str):
+        _check(lib().r360_graph_load(self.h, path.encode()), "graph_load")

@@ -391,6 +391,50 @@ int launch_gicp_pass(hipStream_t st, const GicpCloud& S, const GicpCloud& T, con
                      const double* M6, double* partials, double* sums);
 int launch_gicp_sum(hipStream_t st, const double* v, size_t n, double* partials, double* sums);
 
+// ------------------------------------------------------------------ pose-graph optimisation (kernels/pgo_kernels.hip, host/pgo.cpp)
+constexpr int R360_PGO_SLOT_H = 144;    // per-edge slot: the four 6x6 products Ja^T Omega Jc, (a, c) in (i, j) x (i, j)
+constexpr int R360_PGO_SLOT_B = 12;     // the two 6-vectors Ja^T Omega e
+constexpr int R360_PGO_SLOT_LIN = 57;   // e (6), Omega e (6), then R_E, Jr^-1, -R_Z^T, R_Z^T [t_B]x, -Jr^-1 R_B^T (9 each)
+constexpr int R360_PGO_CG1_TPB = 1024;  // the single-workgroup PCG's threads
+constexpr int R360_PGO_CG1_LDS = 65536 - 512;   // dynamic LDS it may take: four vectors of 6 n_free doubles
+constexpr int R360_PGO_CGM_TPB = 192;   // multi-launch PCG: 32 block rows per workgroup
+constexpr int R360_PGO_MAXB = 256;      // workgroups (= partial sums) of the cost reduction at most
+// What the kernels read of one optimise call: every array is sized by the graph alone and rebuilt per call.
+struct PgoDev {
+    int n = 0, m = 0, nf = 0, nnzb = 0;   // vertices, edges, free vertices, blocks of H
+    int2* ij = nullptr;           // [m] the edge's vertices
+    double* Z = nullptr;          // [m][12] row-major 3x4 measurement
+    double* Om = nullptr;         // [m][36] information, symmetric
+    int* vfree = nullptr;         // [nf] the free vertices
+    int* fidx = nullptr;          // [n] free index of a vertex, -1 fixed
+    int* vptr = nullptr;          // [nf + 1] by-vertex entries, in edge order
+    int* ventry = nullptr;        //   edge * 2 + side (0 = i, 1 = j)
+    int* vblk = nullptr;          //   the block of H that takes the entry's off-diagonal product, -1 if the other end is fixed
+    int* rowptr = nullptr;        // [nf + 1] block-CSR rows
+    int* colidx = nullptr;        // [nnzb] free index of the block column, ascending
+    int* diag = nullptr;          // [nf] the row's diagonal block
+    double* Hs = nullptr;         // [m][R360_PGO_SLOT_H]
+    double* bs = nullptr;         // [m][R360_PGO_SLOT_B]
+    double* lin = nullptr;        // [m][R360_PGO_SLOT_LIN]
+    double* cost = nullptr;       // [m] e^T Omega e
+    double* vals = nullptr;       // [nnzb][36] row-major blocks of H
+    double* b = nullptr;          // [6 nf]
+    double* minv = nullptr;       // [nf][36] (H_kk + lambda I)^-1
+};
+// the multi-launch PCG's scalars, every one written by workgroup 0 of one launch and read by later launches
+struct PgoCgState { double rz[2], bb, rr; int iters, done, pad[2]; };
+// one trial's read-back
+struct PgoOut { double F, pred, maxdiag, maxb, bb, rr; int cg_iters, cg_done, pad[2]; };
+int launch_pgo_linearise(hipStream_t st, const PgoDev& D, const double* poses, bool cost_only, double* partials, double* F);
+int launch_pgo_assemble(hipStream_t st, const PgoDev& D, PgoOut* out);
+int launch_pgo_precond(hipStream_t st, const PgoDev& D, double lambda);
+int launch_pgo_cg1(hipStream_t st, const PgoDev& D, double lambda, double tol2, int maxit, double* delta, PgoOut* out);
+// multi-launch PCG: vec = x, r, z, q, p0, p1 (6 nf each), partials [3][workgroups]; *h_state is pinned
+int launch_pgo_cgm(r360_ctx* ctx, const PgoDev& D, double lambda, double tol2, int maxit, double* vec, double* partials,
+                   PgoCgState* d_state, PgoCgState* h_state, PgoOut* out);
+int launch_pgo_update(hipStream_t st, const PgoDev& D, const double* poses, const double* delta, double lambda,
+                      double* trial, PgoOut* out);
+
 // ------------------------------------------------------------------ host objects
 struct r360_plane_queue;
 struct VoxSlot;
