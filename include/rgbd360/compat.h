@@ -30,6 +30,8 @@
 #include <string>
 
 using r360::Calib360;
+using r360::Calibration;
+using r360::ControlPlanes;
 using r360::FilterPointCloud;
 using r360::GeneralizedIterativeClosestPoint;
 using r360::Frame360;

@@ -32,11 +32,13 @@
 #pragma once
 #include <rgbd360_hip.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iostream>
 #include <limits>
 #include <ostream>
 #include <map>
@@ -353,6 +355,12 @@ class Frame360 {
     void buildSphereCloud() { check(r360_frame_build(h_, R360_BUILD_UNDISTORT | R360_BUILD_CLOUD), "buildSphereCloud"); }
     void getPlanes() {
         check(r360_frame_build(h_, R360_BUILD_UNDISTORT | R360_BUILD_PLANES), "getPlanes");
+        fetch_planes();
+    }
+    // getLocalPlanes (GetControlPlanes.cpp:345): getPlanes that also keeps each sensor's planes as they were before
+    // groupPlanes, for ControlPlanes::collect
+    void getLocalPlanes() {
+        check(r360_frame_build(h_, R360_BUILD_UNDISTORT | R360_BUILD_PLANES | R360_BUILD_LOCAL_PLANES), "getLocalPlanes");
         fetch_planes();
     }
     // ---- keyframe persistence (Frame360.h:181-228, 312-345)
@@ -948,6 +956,216 @@ class GraphOptimizer {
     Context* ctx_;
     r360_graph* h_ = nullptr;
     r360_graph_stats stats_ = r360_graph_stats();
+};
+
+// ------------------------------------------------------------------ ControlPlanes / Calibration
+// include/Calibration.h with its members, over r360_rigcal_* (restated in fp64: DESIGN.md §5e), so that the calls of
+// Calibration/Calibrator.cpp:64-75, 176-192 compile unchanged.  CMatrixDouble is the little of
+// mrpt::math::CMatrixDouble those call sites use.
+struct CMatrixDouble {
+    std::vector<double> v;              // row-major
+    size_t rows = 0, cols = 0;
+    CMatrixDouble() = default;
+    CMatrixDouble(size_t r, size_t c) : v(r * c, 0.0), rows(r), cols(c) {}
+    size_t getRowCount() const { return rows; }
+    size_t getColCount() const { return cols; }
+    void setSize(size_t r, size_t c) { v.assign(r * c, 0.0); rows = r; cols = c; }
+    double& operator()(size_t r, size_t c) { return v[r * cols + c]; }
+    double operator()(size_t r, size_t c) const { return v[r * cols + c]; }
+    void loadFromTextFile(const std::string& path) {
+        int nr = 0, nc = 0;
+        check(r360_rigcal_read_matrix(path.c_str(), nullptr, 0, &nr, &nc), "CMatrixDouble::loadFromTextFile");
+        setSize(size_t(nr), size_t(nc));
+        check(r360_rigcal_read_matrix(path.c_str(), v.data(), v.size(), &nr, &nc), "CMatrixDouble::loadFromTextFile");
+    }
+    void saveToTextFile(const std::string& path) const {
+        check(r360_rigcal_write_matrix(path.c_str(), v.data(), int(rows), int(cols)), "CMatrixDouble::saveToTextFile");
+    }
+};
+
+class ControlPlanes {
+  public:
+    // mmCorrespondences[i][j], i < j: one row per pair of planes seen by both sensors (Calibration.h:47-52)
+    std::map<unsigned, std::map<unsigned, CMatrixDouble> > mmCorrespondences;
+    float conditioning[8];              // of the adjacent pairs' normal covariances (the pair (0, 7) under 7)
+    ControlPlanes() { std::fill(conditioning, conditioning + 8, 1.f); }
+    void loadPlaneCorrespondences(const std::string planeCorrespDirectory) {
+        mmCorrespondences.clear();
+        for (unsigned i = 0; i < 7; ++i) {
+            mmCorrespondences[i] = std::map<unsigned, CMatrixDouble>();
+            for (unsigned j = i + 1; j < 8; ++j) {
+                const std::string f = format("%s/correspondences_%u_%u.txt", planeCorrespDirectory.c_str(), i, j);
+                if (FILE* t = std::fopen(f.c_str(), "r")) {
+                    std::fclose(t);
+                    mmCorrespondences[i][j].loadFromTextFile(f);
+                }
+            }
+        }
+    }
+    void savePlaneCorrespondences(const std::string& planeCorrespDirectory) {
+        for (auto& a : mmCorrespondences)
+            for (auto& b : a.second)
+                if (b.second.getRowCount() > 0)
+                    b.second.saveToTextFile(format("%s/correspondences_%u_%u.txt", planeCorrespDirectory.c_str(), a.first, b.first));
+    }
+    // The live form of the pair fit (Calibration/OnlinePairCalibrator.cpp:84-160) with this class's thresholds; the
+    // draw is the library's counter-based hash of (seed, trial, redraw).  3 rows or fewer, or no non-degenerate
+    // draw, leave the matrix untouched.
+    void trimOutliersRANSAC(CMatrixDouble& matched_planes, unsigned seed = 0) {
+        if (matched_planes.getRowCount() <= 3) return;
+        if (matched_planes.getColCount() != 10) throw std::invalid_argument("trimOutliersRANSAC: a correspondence matrix has 10 columns");
+        std::shared_ptr<Context> ctx = default_context_ptr();
+        r360_rigcal* h = nullptr;
+        check(r360_rigcal_create(ctx->get(), &h), "r360_rigcal_create");
+        int n = 0;
+        int rc = r360_rigcal_set_pair(h, 0, 1, matched_planes.v.data(), int(matched_planes.rows), 10);
+        if (!rc) rc = r360_rigcal_trim(h, 0, 1, nullptr, seed, &trim_stats, nullptr, 0);
+        if (!rc) rc = r360_rigcal_get_pair(h, 0, 1, nullptr, 0, &n);
+        if (!rc) {
+            matched_planes.setSize(size_t(n), 10);
+            rc = r360_rigcal_get_pair(h, 0, 1, matched_planes.v.data(), n, &n);
+        }
+        r360_rigcal_destroy(h);
+        check(rc, "ControlPlanes::trimOutliersRANSAC");
+    }
+    // GetControlPlanes.cpp:358-469 on a frame built with getLocalPlanes(): the pairs of planes seen by two sensors at
+    // once are appended to mmCorrespondences and `conditioning` is updated.  Returns the rows added.
+    int collect(Frame360& frame, const r360_rigcal_collect_params* params = nullptr) {
+        if (!collector_) {
+            r360_rigcal* h = nullptr;
+            collector_ctx_ = default_context_ptr();
+            check(r360_rigcal_create(collector_ctx_->get(), &h), "r360_rigcal_create");
+            collector_.reset(h, r360_rigcal_destroy);
+        }
+        int added[28], total = 0, p = 0;
+        check(r360_rigcal_add_frame(collector_.get(), frame.get(), params, added), "ControlPlanes::collect");
+        std::vector<double> rows;
+        for (unsigned i = 0; i < 7; ++i)
+            for (unsigned j = i + 1; j < 8; ++j, ++p) {
+                if (!added[p]) continue;
+                int n = 0;
+                check(r360_rigcal_get_pair(collector_.get(), int(i), int(j), nullptr, 0, &n), "r360_rigcal_get_pair");
+                rows.resize(size_t(n) * 10);
+                check(r360_rigcal_get_pair(collector_.get(), int(i), int(j), rows.data(), n, &n), "r360_rigcal_get_pair");
+                CMatrixDouble& m = mmCorrespondences[i][j];
+                if (m.getRowCount() == 0) m.setSize(0, 10);
+                m.v.insert(m.v.end(), rows.end() - size_t(added[p]) * 10, rows.end());
+                m.rows += size_t(added[p]);
+                total += added[p];
+            }
+        check(r360_rigcal_conditioning(collector_.get(), conditioning), "r360_rigcal_conditioning");
+        return total;
+    }
+    void printConditioning() {
+        std::cout << "Conditioning";
+        for (unsigned k = 0; k < 7; ++k) std::cout << " " << k << "-" << k + 1 << " " << conditioning[k];
+        std::cout << " 0-7 " << conditioning[7] << std::endl;
+    }
+    r360_rigcal_trim_stats trim_stats = r360_rigcal_trim_stats();
+  private:
+    std::shared_ptr<Context> collector_ctx_;      // declared before collector_: the handle goes first
+    std::shared_ptr<r360_rigcal> collector_;      // holds the collected rows' normal covariances between frames
+};
+
+class Calibration {
+  public:
+    ControlPlanes matchedPlanes;
+    Matrix4f Rt_specs[8];               // the construction specifications
+    Matrix4f Rt_estimated[8];           // what the calibration estimates
+    Calibration() : keep_(default_context_ptr()) { check(r360_rigcal_create(keep_->get(), &h_), "r360_rigcal_create"); }
+    ~Calibration() { r360_rigcal_destroy(h_); }
+    Calibration(const Calibration&) = delete;
+    Calibration& operator=(const Calibration&) = delete;
+    void loadConstructionSpecs() {
+        double rt[128];
+        r360_rigcal_specs(rt);
+        for (int k = 0; k < 8; ++k)
+            for (int i = 0; i < 16; ++i) Rt_specs[k].v[i] = float(rt[16 * k + i]);
+        specs_loaded_ = true;
+    }
+    // weightedLS = 1 weights the normal equations only when every matrix has 18 columns, the reference's own
+    // condition (Calibration.h:1086), which its 10-column files never meet
+    void CalibrateRotation(int weightedLS = 0) {
+        const bool weighted = push_rows() && weightedLS == 1;
+        double rt[128];
+        r360_rigcal_specs(rt);           // the specs in double unless the caller changed Rt_specs
+        // Rt_specs is a float member, as in the reference; the solve starts from doubles.  Invariant: an entry that
+        // still equals float(spec) is taken to be the untouched spec and gets the spec's double; an entry the
+        // caller changed to any other float is used as given.  (A caller's value that happens to equal the float
+        // rounding of the spec therefore becomes the spec, which differs from it by less than one float ulp.)
+        for (int k = 0; k < 8; ++k)
+            for (int i = 0; i < 16; ++i)
+                if (!specs_loaded_ || Rt_specs[k].v[i] != float(rt[16 * k + i])) rt[16 * k + i] = Rt_specs[k].v[i];
+        check(r360_rigcal_set_init(h_, rt), "Calibration::CalibrateRotation");
+        const int rc = r360_rigcal_rotation(h_, weighted ? 1 : 0, &rotation_stats);
+        pull_estimate();
+        check(rc, "Calibration::CalibrateRotation");
+        const r360_rigcal_stats& s = rotation_stats;
+        if (s.iterations > 0)
+            std::cout << "ErrorCalibRotation " << (s.status == R360_RIGCAL_BAD_CONDITIONED ? s.error : s.werr0)[s.iterations - 1] / s.rows << " "
+                      << s.angle[s.iterations - 1] / s.rows << std::endl;   // accum_error2 as :1157 or :1082 left it
+    }
+    void CalibrateTranslation(int weightedLS = 0) {
+        const bool weighted = push_rows() && weightedLS == 1;
+        push_estimate();
+        const int rc = r360_rigcal_translation(h_, weighted ? 1 : 0, &translation_stats);
+        pull_estimate();
+        check(rc, "Calibration::CalibrateTranslation");
+        const r360_rigcal_stats& s = translation_stats;
+        if (s.status == R360_RIGCAL_CONVERGED) std::cout << "ErrorCalibTranslation " << s.error[0] / s.rows << std::endl;
+        else std::cout << "\tTranslation system is bad conditioned " << s.conditioning[0] << " threshold 8000\n";
+    }
+    void Calibrate() {
+        CalibrateRotation();
+        CalibrateTranslation();
+    }
+    // the estimate in double, column-major [8][16], and as the Rt_0k.txt files loadExtrinsicCalibration reads
+    void getEstimate(double rt8[128]) const { check(r360_rigcal_get_estimate(h_, rt8), "Calibration::getEstimate"); }
+    void saveExtrinsics(const std::string& dir) {
+        push_estimate();
+        check(r360_rigcal_save_extrinsics(h_, dir.c_str()), "Calibration::saveExtrinsics");
+    }
+    r360_rigcal* get() const { return h_; }
+    r360_rigcal_stats rotation_stats = r360_rigcal_stats(), translation_stats = r360_rigcal_stats();
+  private:
+    // the matrices' first ten columns into the handle; true when every matrix has 18 columns
+    bool push_rows() {
+        check(r360_rigcal_clear(h_), "r360_rigcal_clear");
+        bool all18 = true;
+        std::vector<double> rows;
+        for (auto& a : matchedPlanes.mmCorrespondences)
+            for (auto& b : a.second) {
+                const CMatrixDouble& m = b.second;
+                if (m.getRowCount() == 0) continue;
+                if (m.getColCount() < 10) throw std::invalid_argument("Calibration: a correspondence matrix has at least 10 columns");
+                all18 = all18 && m.getColCount() == 18;
+                rows.resize(m.getRowCount() * 10);
+                for (size_t r = 0; r < m.getRowCount(); ++r)
+                    for (size_t c = 0; c < 10; ++c) rows[r * 10 + c] = m(r, c);
+                check(r360_rigcal_set_pair(h_, int(a.first), int(b.first), rows.data(), int(m.getRowCount()), 10), "r360_rigcal_set_pair");
+            }
+        return all18;
+    }
+    void pull_estimate() {
+        check(r360_rigcal_get_estimate(h_, est_), "r360_rigcal_get_estimate");
+        for (int k = 0; k < 8; ++k)
+            for (int i = 0; i < 16; ++i) Rt_estimated[k].v[i] = float(est_[16 * k + i]);
+    }
+    // Rt_estimated back into the handle where the caller changed it; untouched entries keep their doubles (the same
+    // invariant as for Rt_specs above: equal to float(double) means untouched)
+    void push_estimate() {
+        double rt[128];
+        check(r360_rigcal_get_estimate(h_, rt), "r360_rigcal_get_estimate");
+        bool changed = false;
+        for (int k = 0; k < 8; ++k)
+            for (int i = 0; i < 16; ++i)
+                if (Rt_estimated[k].v[i] != float(rt[16 * k + i])) { rt[16 * k + i] = Rt_estimated[k].v[i]; changed = true; }
+        if (changed) check(r360_rigcal_set_init(h_, rt), "r360_rigcal_set_init");
+    }
+    std::shared_ptr<Context> keep_;     // declared before h_: the handle goes first, then its context
+    r360_rigcal* h_ = nullptr;
+    double est_[128];
+    bool specs_loaded_ = false;
 };
 
 }  // namespace r360

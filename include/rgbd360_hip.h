@@ -73,6 +73,7 @@ enum {
     R360_BUILD_CLOUD     = 1u << 3,  /* Frame360::buildSphereCloud()     Frame360.h:467   */
     R360_BUILD_PLANES    = 1u << 4,  /* Frame360::getPlanes()            Frame360.h:615   */
     R360_BUILD_SENSOR_PYRAMID = 1u << 5, /* per-sensor setSource/TargetFrame (pinhole alignFrames) */
+    R360_BUILD_LOCAL_PLANES = 1u << 6,   /* with R360_BUILD_PLANES: keep each sensor's planes as they were before groupPlanes (r360_frame_get_local_planes) */
     /* Reported by r360_frame_built only (not a stage to ask for): the sphere images and level 0's {gray, depth}
      * image are in HBM.  Clear after the build of a frame that only enters batched alignments
      * (r360_frame_set_compaction(f, 0)) where those passes stream level 0's packed image: such a build writes
@@ -312,6 +313,12 @@ typedef struct {
 } r360_plane;
 
 int r360_frame_get_planes(r360_frame* f, r360_plane* out, int cap, int* n);
+/* The planes of one sensor as getPlanesSensor left them, before groupPlanes / mergePlanes, of a frame built with
+ * R360_BUILD_PLANES | R360_BUILD_LOCAL_PLANES (R360_EINVAL without the flag): normal, center, d and ppal taken back
+ * to the SENSOR's frame with the build's own Rt_k.  labels: the region labels (r360_frame_get_labels' labf, within
+ * the sensor's image) merged into plane `plane`, in merge order. */
+int r360_frame_get_local_planes(r360_frame* f, int sensor, r360_plane* out, int cap, int* n);
+int r360_frame_get_local_plane_labels(r360_frame* f, int sensor, int plane, int* labels, int cap, int* n);
 /* Plane::label of plane i (set by the labelization tools, LabelizeFrame360.cpp).  get returns the
  * label length and copies at most cap-1 bytes plus a terminator. */
 int r360_frame_set_plane_label(r360_frame* f, int i, const char* label);
@@ -821,6 +828,100 @@ int  r360_g2o_read(const char* path, double* poses, int* fixed, int cap_vertices
 /* saveGraph / the matching load: load replaces the graph's vertices and edges. */
 int  r360_graph_save(const r360_graph* g, const char* path);
 int  r360_graph_load(r360_graph* g, const char* path);
+
+/* ---------------------------------------------------------------- rig extrinsic calibration from control planes
+ * include/Calibration.h (ControlPlanes, Calibration: loadConstructionSpecs :918-930, CalibrateRotation :1026-1218,
+ * CalibrateTranslation :1222-1334, calcConditioning :1346-1352) restated in fp64: the statement is
+ * tests/rigcal_model.py and DESIGN.md §5e.  A correspondence row has ten doubles: n_i (3), d_i, n_ii (3), d_ii in the
+ * two sensors' own frames, the smaller inlier count and the pixel-centre figure.  Pairs are (i, j), 0 <= i < j < 8, as
+ * the reference's mmCorrespondences[i][j]; poses are COLUMN-major double[16], eight of them.
+ * The per-row terms and every sum run on the context's GPU in a fixed order (two runs give the same bytes); the
+ * 21x21 solve, its conditioning and the Rodrigues update stay on the host.  A handle created with ctx NULL holds rows
+ * and files only: every call that needs the GPU returns R360_EINVAL on it.
+ * R360_EMISSING_PAIR: an adjacent pair (k, k+1), k = 0..6, has fewer than 3 rows (the reference asserts). */
+#define R360_EMISSING_PAIR (-6)
+#define R360_RIGCAL_MAX_ITERATIONS 10
+typedef struct r360_rigcal r360_rigcal;
+enum { R360_RIGCAL_CONVERGED = 0, R360_RIGCAL_ITERATION_LIMIT = 1, R360_RIGCAL_BAD_CONDITIONED = 2, R360_RIGCAL_MISSING_PAIR = 3 };
+typedef struct {
+    int status;        /* R360_RIGCAL_* */
+    int iterations;    /* linearisations made (rotation: up to 10; translation: 1) */
+    int rows;          /* correspondence rows in all */
+    int pad;
+    /* per iteration: sum |r|^2, sum of the angles (rotation only), sigma_max / sigma_min of the 21x21 matrix,
+     * |update|^2, the weighted error before and after the step (rotation only), whether the step was applied */
+    double error[R360_RIGCAL_MAX_ITERATIONS], angle[R360_RIGCAL_MAX_ITERATIONS], conditioning[R360_RIGCAL_MAX_ITERATIONS];
+    double update2[R360_RIGCAL_MAX_ITERATIONS], werr0[R360_RIGCAL_MAX_ITERATIONS], werr1[R360_RIGCAL_MAX_ITERATIONS];
+    int accepted[R360_RIGCAL_MAX_ITERATIONS];
+} r360_rigcal_stats;
+typedef struct {
+    double dist;         /* 0.2: |d| threshold; the normals' threshold is dist / 2 (Calibration.h:196) */
+    double degenerate;   /* 0.3: a draw with |n1 . (n2 x n3)| below it is redrawn (:221) */
+    double prob;         /* 0.99 (:257) */
+    int max_iterations;  /* 5000 (:258) */
+    int max_redraws;     /* 100 per trial */
+    int chunk;           /* trials per launch; 0 = 256.  The outcome does not depend on it. */
+    int pad;
+} r360_rigcal_trim_params;
+typedef struct { int inliers, trials, winner, no_model; } r360_rigcal_trim_stats;
+int  r360_rigcal_create(r360_ctx* ctx, r360_rigcal** out);
+void r360_rigcal_destroy(r360_rigcal* h);
+/* A pair's rows [n][cols] row-major; cols must be 10; n = 0 removes the pair.  get: *n is set either way, cap (in
+ * rows) < *n with rows given is an error. */
+int  r360_rigcal_set_pair(r360_rigcal* h, int i, int j, const double* rows, int n, int cols);
+int  r360_rigcal_get_pair(const r360_rigcal* h, int i, int j, double* rows, int cap, int* n);
+int  r360_rigcal_clear(r360_rigcal* h);
+/* 0, or R360_EMISSING_PAIR; host only. */
+int  r360_rigcal_check(const r360_rigcal* h);
+/* loadPlaneCorrespondences / savePlaneCorrespondences (Calibration.h:276-323): dir/correspondences_%u_%u.txt, text
+ * matrices, one row per line, %.16e.  Host only.  load replaces every pair; save writes the pairs that have rows. */
+int  r360_rigcal_load_dir(r360_rigcal* h, const char* dir);
+int  r360_rigcal_save_dir(const r360_rigcal* h, const char* dir);
+/* One such text matrix, no handle needed.  read: rows may be NULL (count only); cap in doubles. */
+int  r360_rigcal_read_matrix(const char* path, double* rows, size_t cap, int* n_rows, int* n_cols);
+int  r360_rigcal_write_matrix(const char* path, const double* rows, int n_rows, int n_cols);
+/* loadConstructionSpecs. */
+void r360_rigcal_specs(double rt8[8 * 16]);
+/* The starting extrinsics of CalibrateRotation (a new handle holds the specs) and the current estimate. */
+int  r360_rigcal_set_init(r360_rigcal* h, const double rt8[8 * 16]);
+int  r360_rigcal_get_estimate(const r360_rigcal* h, double rt8[8 * 16]);
+/* The estimate as dir/Rt_0{1..8}.txt, the files r360_calib_load_extrinsics reads.  Host only. */
+int  r360_rigcal_save_extrinsics(const r360_rigcal* h, const char* dir);
+/* CalibrateRotation(weighted): starts from the init extrinsics.  CalibrateTranslation(weighted): on the current
+ * estimate's rotations; applied only when the conditioning is below 8000.  weighted is a plain flag (the reference
+ * also asks for 18 columns).  Return 0 with stats->status set, or R360_EMISSING_PAIR (stats->status says so too). */
+int  r360_rigcal_rotation(r360_rigcal* h, int weighted, r360_rigcal_stats* stats);
+int  r360_rigcal_translation(r360_rigcal* h, int weighted, r360_rigcal_stats* stats);
+void r360_rigcal_default_trim_params(r360_rigcal_trim_params* p);
+/* trimOutliersRANSAC on one pair's rows, the live form of the fit (Calibration/OnlinePairCalibrator.cpp:84-160), a
+ * counter-based hash of (seed, trial, redraw) for the draw.  The pair keeps its inliers, in order; mask [cap] (may be
+ * NULL) gets one byte per former row.  3 rows or fewer, or no non-degenerate trial (no_model), leave it untouched. */
+int  r360_rigcal_trim(r360_rigcal* h, int i, int j, const r360_rigcal_trim_params* params, unsigned seed,
+                      r360_rigcal_trim_stats* stats, unsigned char* mask, int cap);
+/* The collector, GetControlPlanes.cpp:358-469, on a frame built with R360_BUILD_PLANES | R360_BUILD_LOCAL_PLANES (on
+ * the handle's device; R360_EINVAL without the flag): for sensors s1 < s2 and their local planes i, j, a row is added
+ * when both have more than min_inliers pixels and an elongation below max_elongation, their rig-frame normals have a
+ * dot product above min_dot and their rig-frame distances differ by less than max_dist.  Columns: the planes'
+ * sensor-frame normal and d (r360_frame_get_local_planes), the smaller pixel count, and the larger of the two means of
+ * (row + col) over a plane's pixels in its sensor's organised cloud, counted on the GPU over the final label image.
+ * added[28] (may be NULL): rows added per pair.  conditioning: sigma_max / sigma_min of the adjacent pairs' sums of
+ * n_i n_j^T (rig frame) over the rows collected so far, the pair (0, 7) under index 7 (:446-462); 1 before any row. */
+typedef struct {
+    int min_inliers;        /* 1000 */
+    int pad;
+    double max_elongation;  /* 5 */
+    double min_dot;         /* 0.99 */
+    double max_dist;        /* 0.2 */
+} r360_rigcal_collect_params;
+void r360_rigcal_default_collect_params(r360_rigcal_collect_params* p);
+int  r360_rigcal_add_frame(r360_rigcal* h, r360_frame* frame, const r360_rigcal_collect_params* params, int* added);
+int  r360_rigcal_conditioning(const r360_rigcal* h, float conditioning[8]);
+/* Parity hooks.  eval: mode 0 rotation, 1 translation, at the current estimate: H [21][21] row-major, g [21],
+ * scalars [4] = sum of squared residuals, sum of angles, rows, weighted error.  ransac_eval: trials [trial0, trial0 +
+ * n) of a pair: the inlier count and the no-draw flag of each. */
+int  r360_rigcal_eval(r360_rigcal* h, int mode, int weighted, double* H, double* g, double* scalars);
+int  r360_rigcal_ransac_eval(r360_rigcal* h, int i, int j, const r360_rigcal_trim_params* params, unsigned seed,
+                             int trial0, int n, int* counts, int* flags);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ REPO_ROOT = os.path.dirname(_HERE)
 PHOTO_CONSISTENCY, DEPTH_CONSISTENCY, PHOTO_DEPTH = 0, 1, 2
 BUILD_UNDISTORT, BUILD_SPHERE, BUILD_PYRAMID, BUILD_CLOUD, BUILD_PLANES = 1, 2, 4, 8, 16
 BUILD_SENSOR_PYRAMID = 32
+BUILD_LOCAL_PLANES = 64
 BUILT_LEVEL0 = 256   # reported by Frame360.built() only: the sphere images and level 0's {gray, depth} are in HBM
 PCD_ASCII, PCD_BINARY, PCD_BINARY_COMPRESSED = 0, 1, 2
 
@@ -106,6 +107,54 @@ class GraphStats(C.Structure):
 
 
 GRAPH_CONVERGED, GRAPH_ITERATION_LIMIT, GRAPH_STALLED, GRAPH_CG_NOT_CONVERGED = 0, 1, 2, 3
+
+
+class RigcalStats(C.Structure):
+    """r360_rigcal_stats — what one r360_rigcal_rotation / _translation did (per-iteration arrays of 10)."""
+    _fields_ = [
+        ("status", C.c_int), ("iterations", C.c_int), ("rows", C.c_int), ("pad", C.c_int),
+        ("error", C.c_double * 10), ("angle", C.c_double * 10), ("conditioning", C.c_double * 10),
+        ("update2", C.c_double * 10), ("werr0", C.c_double * 10), ("werr1", C.c_double * 10), ("accepted", C.c_int * 10),
+    ]
+
+
+class RigcalTrimParams(C.Structure):
+    """r360_rigcal_trim_params — the outlier trimmer's settings (see include/rgbd360_hip.h)."""
+    _fields_ = [
+        ("dist", C.c_double), ("degenerate", C.c_double), ("prob", C.c_double), ("max_iterations", C.c_int),
+        ("max_redraws", C.c_int), ("chunk", C.c_int), ("pad", C.c_int),
+    ]
+
+    @classmethod
+    def default(cls, **kw) -> "RigcalTrimParams":
+        p = cls()
+        lib().r360_rigcal_default_trim_params(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+
+class RigcalCollectParams(C.Structure):
+    """r360_rigcal_collect_params — the collector's thresholds (GetControlPlanes.cpp:386-389)."""
+    _fields_ = [("min_inliers", C.c_int), ("pad", C.c_int), ("max_elongation", C.c_double), ("min_dot", C.c_double),
+                ("max_dist", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw) -> "RigcalCollectParams":
+        p = cls()
+        lib().r360_rigcal_default_collect_params(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+
+class RigcalTrimStats(C.Structure):
+    """r360_rigcal_trim_stats — what one r360_rigcal_trim did."""
+    _fields_ = [("inliers", C.c_int), ("trials", C.c_int), ("winner", C.c_int), ("no_model", C.c_int)]
+
+
+RIGCAL_CONVERGED, RIGCAL_ITERATION_LIMIT, RIGCAL_BAD_CONDITIONED, RIGCAL_MISSING_PAIR = 0, 1, 2, 3
+EMISSING_PAIR = -6
 
 
 class MatchParams(C.Structure):
@@ -378,6 +427,33 @@ _SIGS = [
     ("r360_g2o_read", C.c_int, [C.c_char_p, _DP, _IP, C.c_int, _IP, _IP, _DP, _DP, C.c_int, _IP]),
     ("r360_graph_save", C.c_int, [_P, C.c_char_p]),
     ("r360_graph_load", C.c_int, [_P, C.c_char_p]),
+    ("r360_rigcal_create", C.c_int, [_P, C.POINTER(_P)]),
+    ("r360_rigcal_destroy", None, [_P]),
+    ("r360_rigcal_set_pair", C.c_int, [_P, C.c_int, C.c_int, _DP, C.c_int, C.c_int]),
+    ("r360_rigcal_get_pair", C.c_int, [_P, C.c_int, C.c_int, _DP, C.c_int, _IP]),
+    ("r360_rigcal_clear", C.c_int, [_P]),
+    ("r360_rigcal_check", C.c_int, [_P]),
+    ("r360_rigcal_load_dir", C.c_int, [_P, C.c_char_p]),
+    ("r360_rigcal_save_dir", C.c_int, [_P, C.c_char_p]),
+    ("r360_rigcal_read_matrix", C.c_int, [C.c_char_p, _DP, C.c_size_t, _IP, _IP]),
+    ("r360_rigcal_write_matrix", C.c_int, [C.c_char_p, _DP, C.c_int, C.c_int]),
+    ("r360_rigcal_specs", None, [_DP]),
+    ("r360_rigcal_set_init", C.c_int, [_P, _DP]),
+    ("r360_rigcal_get_estimate", C.c_int, [_P, _DP]),
+    ("r360_rigcal_save_extrinsics", C.c_int, [_P, C.c_char_p]),
+    ("r360_rigcal_rotation", C.c_int, [_P, C.c_int, C.POINTER(RigcalStats)]),
+    ("r360_rigcal_translation", C.c_int, [_P, C.c_int, C.POINTER(RigcalStats)]),
+    ("r360_rigcal_default_trim_params", None, [C.POINTER(RigcalTrimParams)]),
+    ("r360_rigcal_trim", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(RigcalTrimParams), C.c_uint,
+                                   C.POINTER(RigcalTrimStats), C.c_void_p, C.c_int]),
+    ("r360_rigcal_eval", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP, _DP]),
+    ("r360_rigcal_default_collect_params", None, [C.POINTER(RigcalCollectParams)]),
+    ("r360_rigcal_add_frame", C.c_int, [_P, _P, C.POINTER(RigcalCollectParams), _IP]),
+    ("r360_rigcal_conditioning", C.c_int, [_P, _FP]),
+    ("r360_frame_get_local_planes", C.c_int, [_P, C.c_int, C.POINTER(Plane), C.c_int, _IP]),
+    ("r360_frame_get_local_plane_labels", C.c_int, [_P, C.c_int, C.c_int, _IP, C.c_int, _IP]),
+    ("r360_rigcal_ransac_eval", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(RigcalTrimParams), C.c_uint, C.c_int, C.c_int,
+                                          _IP, _IP]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -853,6 +929,24 @@ class Frame360:
         dist = np.zeros((8, h, w), np.float32)
         _check(lib().r360_frame_get_cloud(self.h, _fptr(xyz), _vptr(rgb), _fptr(nrm), _fptr(dist)), "get_cloud")
         return xyz, rgb, nrm, dist
+
+    def localPlanes(self, sensor: int) -> list[dict]:
+        """r360_frame_get_local_planes (a build with BUILD_PLANES | BUILD_LOCAL_PLANES): the sensor's planes before
+        groupPlanes, in the sensor's frame, each with the region labels merged into it."""
+        n = C.c_int()
+        _check(lib().r360_frame_get_local_planes(self.h, sensor, None, 0, C.byref(n)), "get_local_planes")
+        arr = (Plane * max(n.value, 1))()
+        _check(lib().r360_frame_get_local_planes(self.h, sensor, arr, n.value, C.byref(n)), "get_local_planes")
+        out = []
+        for i, p in enumerate(arr[:n.value]):
+            m = C.c_int()
+            _check(lib().r360_frame_get_local_plane_labels(self.h, sensor, i, None, 0, C.byref(m)), "get_local_plane_labels")
+            lab = np.zeros(max(m.value, 1), np.int32)
+            _check(lib().r360_frame_get_local_plane_labels(self.h, sensor, i, lab.ctypes.data_as(_IP), m.value, C.byref(m)),
+                   "get_local_plane_labels")
+            out.append(dict(normal=np.array(p.normal[:], np.float32), center=np.array(p.center[:], np.float32), d=np.float32(p.d),
+                            elongation=p.elongation, n_inliers=p.n_inliers, labels=lab[:m.value].copy()))
+        return out
 
     def labels(self):
         h, w = self.rows // 2, self.cols // 2
@@ -1778,3 +1872,152 @@ class PoseGraph:
 
     def loadGraph(self, path: str):
         _check(lib().r360_graph_load(self.h, path.encode()), "graph_load")
+
+
+def rigcal_read_matrix(path: str) -> np.ndarray:
+    """One of the reference's text matrices (correspondences_i_j.txt) through the library's reader; no GPU."""
+    nr, nc = C.c_int(), C.c_int()
+    _check(lib().r360_rigcal_read_matrix(path.encode(), None, 0, C.byref(nr), C.byref(nc)), "rigcal_read_matrix")
+    a = np.zeros((nr.value, nc.value))
+    _check(lib().r360_rigcal_read_matrix(path.encode(), _dptr(a), a.size, C.byref(nr), C.byref(nc)), "rigcal_read_matrix")
+    return a
+
+
+def rigcal_write_matrix(path: str, rows: np.ndarray):
+    a = np.ascontiguousarray(rows, np.float64)
+    assert a.ndim == 2
+    _check(lib().r360_rigcal_write_matrix(path.encode(), _dptr(a), a.shape[0], a.shape[1]), "rigcal_write_matrix")
+
+
+def rigcal_specs() -> np.ndarray:
+    """loadConstructionSpecs (Calibration.h:918-930): (8, 4, 4) float64."""
+    a = np.zeros(128)
+    lib().r360_rigcal_specs(_dptr(a))
+    return a.reshape(8, 4, 4).transpose(0, 2, 1).copy()
+
+
+class RigCalibration:
+    """The reference's ControlPlanes + Calibration (include/Calibration.h) over r360_rigcal_*: correspondence rows per
+    sensor pair (i, j), i < j, the rotation and translation solves and the outlier trimmer on the context's GPU.
+    ctx None gives a handle for rows and files only.  Extrinsics are (8, 4, 4) float64."""
+
+    def __init__(self, ctx: "Context | None" = None):
+        h = C.c_void_p()
+        _check(lib().r360_rigcal_create(ctx.h if ctx is not None else None, C.byref(h)), "r360_rigcal_create")
+        self.h, self.ctx = h, ctx
+
+    def close(self):
+        if self.h:
+            lib().r360_rigcal_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setPair(self, i: int, j: int, rows):
+        a = np.ascontiguousarray(rows, np.float64).reshape(-1, 10) if len(rows) else np.zeros((0, 10))
+        _check(lib().r360_rigcal_set_pair(self.h, i, j, _dptr(a), a.shape[0], 10), "rigcal_set_pair")
+
+    def getPair(self, i: int, j: int) -> np.ndarray:
+        n = C.c_int()
+        _check(lib().r360_rigcal_get_pair(self.h, i, j, None, 0, C.byref(n)), "rigcal_get_pair")
+        a = np.zeros((n.value, 10))
+        _check(lib().r360_rigcal_get_pair(self.h, i, j, _dptr(a), n.value, C.byref(n)), "rigcal_get_pair")
+        return a
+
+    def setPairs(self, rows: dict):
+        self.clear()
+        for (i, j), r in rows.items():
+            self.setPair(i, j, r)
+
+    def pairs(self) -> dict:
+        out = {}
+        for i in range(8):
+            for j in range(i + 1, 8):
+                r = self.getPair(i, j)
+                if len(r):
+                    out[(i, j)] = r
+        return out
+
+    def clear(self):
+        _check(lib().r360_rigcal_clear(self.h), "rigcal_clear")
+
+    def check(self) -> int:
+        """0, or EMISSING_PAIR when an adjacent pair has fewer than 3 rows."""
+        rc = lib().r360_rigcal_check(self.h)
+        return rc if rc == EMISSING_PAIR else _check(rc, "rigcal_check")
+
+    def loadPlaneCorrespondences(self, path: str):
+        _check(lib().r360_rigcal_load_dir(self.h, path.encode()), "rigcal_load_dir")
+
+    def savePlaneCorrespondences(self, path: str):
+        _check(lib().r360_rigcal_save_dir(self.h, path.encode()), "rigcal_save_dir")
+
+    def setInit(self, rt8):
+        a = np.ascontiguousarray(np.asarray(rt8, np.float64).reshape(8, 4, 4).transpose(0, 2, 1)).reshape(128)
+        _check(lib().r360_rigcal_set_init(self.h, _dptr(a)), "rigcal_set_init")
+
+    def estimate(self) -> np.ndarray:
+        a = np.zeros(128)
+        _check(lib().r360_rigcal_get_estimate(self.h, _dptr(a)), "rigcal_get_estimate")
+        return a.reshape(8, 4, 4).transpose(0, 2, 1).copy()
+
+    def saveExtrinsics(self, path: str):
+        _check(lib().r360_rigcal_save_extrinsics(self.h, path.encode()), "rigcal_save_extrinsics")
+
+    def _solve(self, fn, what, weighted) -> "RigcalStats":
+        st = RigcalStats()
+        rc = fn(self.h, int(weighted), C.byref(st))
+        if rc != EMISSING_PAIR:
+            _check(rc, what)
+        return st
+
+    def CalibrateRotation(self, weighted: bool = False) -> "RigcalStats":
+        return self._solve(lib().r360_rigcal_rotation, "rigcal_rotation", weighted)
+
+    def CalibrateTranslation(self, weighted: bool = False) -> "RigcalStats":
+        return self._solve(lib().r360_rigcal_translation, "rigcal_translation", weighted)
+
+    def Calibrate(self):
+        return self.CalibrateRotation(), self.CalibrateTranslation()
+
+    def trimOutliersRANSAC(self, i: int, j: int, seed: int = 0, params: "RigcalTrimParams | None" = None):
+        """r360_rigcal_trim: (stats, mask over the pair's former rows)."""
+        p = params if params is not None else RigcalTrimParams.default()
+        n = len(self.getPair(i, j))
+        mask = np.ones(max(n, 1), np.uint8)
+        st = RigcalTrimStats()
+        _check(lib().r360_rigcal_trim(self.h, i, j, C.byref(p), seed, C.byref(st), _vptr(mask), n), "rigcal_trim")
+        return st, mask[:n].astype(bool)
+
+    def addFrame(self, frame: "Frame360", params: "RigcalCollectParams | None" = None) -> np.ndarray:
+        """r360_rigcal_add_frame: the collector on a frame built with BUILD_LOCAL_PLANES; rows added per pair [28]."""
+        p = params if params is not None else RigcalCollectParams.default()
+        added = np.zeros(28, np.int32)
+        _check(lib().r360_rigcal_add_frame(self.h, frame.h, C.byref(p), added.ctypes.data_as(_IP)), "rigcal_add_frame")
+        return added
+
+    def conditioning(self) -> np.ndarray:
+        c = np.zeros(8, np.float32)
+        _check(lib().r360_rigcal_conditioning(self.h, _fptr(c)), "rigcal_conditioning")
+        return c
+
+    def eval(self, mode: int, weighted: bool = False):
+        """r360_rigcal_eval at the current estimate: (H [21, 21], g [21], scalars [4]); EMISSING_PAIR when it applies."""
+        H, g, sc = np.zeros((21, 21)), np.zeros(21), np.zeros(4)
+        rc = lib().r360_rigcal_eval(self.h, mode, int(weighted), _dptr(H), _dptr(g), _dptr(sc))
+        if rc == EMISSING_PAIR:
+            return rc
+        _check(rc, "rigcal_eval")
+        return H, g, sc
+
+    def ransacEval(self, i: int, j: int, seed: int, trial0: int, n: int, params: "RigcalTrimParams | None" = None):
+        """r360_rigcal_ransac_eval: (inlier counts [n], no-draw flags [n]) of trials trial0 .. trial0 + n - 1."""
+        p = params if params is not None else RigcalTrimParams.default()
+        counts, flags = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(lib().r360_rigcal_ransac_eval(self.h, i, j, C.byref(p), seed, trial0, n, counts.ctypes.data_as(_IP),
+                                             flags.ctypes.data_as(_IP)), "rigcal_ransac_eval")
+        return counts, flags

@@ -348,6 +348,12 @@ bool hulls_touch(const HPlane& A, const HPlane& B, float max_dist, float max_nor
 struct PbMapHost {
     std::vector<HPlane> planes;
 };
+// planes_assemble_sensor's output kept as it was before groupPlanes / mergePlanes (rig frame), and per plane the
+// labels of the regions merged into it, in merge order
+struct LocalPlanesHost {
+    std::vector<HPlane> planes[8];
+    std::vector<std::vector<int>> labels[8];
+};
 
 // ------------------------------------------------------------------ buffers
 int plane_bufs_alloc(r360_frame* f) {
@@ -423,6 +429,8 @@ void plane_bufs_free(r360_frame* f) {
     P = PlaneBufs();
     delete f->pbmap;
     f->pbmap = nullptr;
+    delete f->local;
+    f->local = nullptr;
 }
 
 int ctx_vhash_reserve(r360_ctx* ctx, long min_cells, long list_entries, long list_groups) {
@@ -615,8 +623,10 @@ extern "C" int r360_frames_build(r360_frame* const* frames, int n, unsigned flag
     }
     r360_ctx* H = frames[0]->ctx;
     if (bind_device(H->device)) return -1;
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
         if (int rc = r360_frame_build_async(frames[i], R360_BUILD_UNDISTORT)) return rc;
+        frames[i]->want_local = (flags & R360_BUILD_LOCAL_PLANES) != 0;
+    }
     if ((int)H->bvox.size() < R360_PLANE_BATCH - 1) H->bvox.resize(R360_PLANE_BATCH - 1);
     for (int i = 0; i < n; ++i)
         if (plane_bufs_alloc(frames[i])) return -1;
@@ -658,7 +668,7 @@ extern "C" int r360_frames_build(r360_frame* const* frames, int n, unsigned flag
         for (r360_frame* f : bf) {
             R360_HIP(hipEventRecord(f->pl.done, H->stream));
             if (planes_spawn_assembly(f)) return -1;
-            f->built |= R360_BUILD_UNDISTORT | plane_flags;
+            f->built = (f->built & ~(unsigned)R360_BUILD_LOCAL_PLANES) | R360_BUILD_UNDISTORT | plane_flags | (flags & R360_BUILD_LOCAL_PLANES);
             delete f->sphere_cloud;   // a cloud set by loadCloud is replaced by the built one
             f->sphere_cloud = nullptr;
         }
@@ -853,6 +863,9 @@ int planes_spawn_assembly(r360_frame* f) {
     PlaneBufs& P = f->pl;
     delete f->pbmap;
     f->pbmap = nullptr;
+    delete f->local;
+    f->local = f->want_local ? new LocalPlanesHost : nullptr;
+    f->want_local = false;
     AsmPool& A = asm_pool();
     {
         std::lock_guard<std::mutex> lk(A.m);
@@ -956,6 +969,8 @@ static void planes_assemble_sensor(r360_frame* f, int s, std::vector<HPlane>& lo
     };
     const float* Rt = f->calib->rt[s];
     local.clear();
+    std::vector<std::vector<int>>* keep = f->local ? &f->local->labels[s] : nullptr;
+    if (keep) keep->clear();
     for (int m = 0; m < P.h_nmodels[s]; ++m) {
         const PlaneOut& O = P.h_out[s * R360_MAX_MODELS + m];
         HPlane pl;
@@ -1002,11 +1017,13 @@ static void planes_assemble_sensor(r360_frame* f, int s, std::vector<HPlane>& lo
                 if (q.curvature < kMaxCurvature && same_plane(q, pl, 0.99f, 0.05f, 0.2f)) {
                     merge_into(q, pl);
                     merged = true;
+                    if (keep) (*keep)[size_t(&q - local.data())].push_back(O.model.label);
                     break;
                 }
         if (!merged) {
             pl.id = int(local.size());
             local.push_back(pl);
+            if (keep) keep->push_back(std::vector<int>(1, O.model.label));
         }
         tick(pf->local, tq);
     }
@@ -1020,6 +1037,8 @@ static int planes_assemble_group(r360_frame* f, std::vector<std::vector<HPlane>>
     const auto t3 = asm_now();
     auto* pm = new PbMapHost;
     std::vector<HPlane>& G = pm->planes;
+    if (f->local)
+        for (int s = 0; s < 8; ++s) f->local->planes[s] = local[s];
     G = local[0];
     std::set<unsigned> first, prev;
     for (const HPlane& p : G) first.insert(unsigned(p.id));
@@ -1394,6 +1413,44 @@ extern "C" int r360_frame_get_planes(r360_frame* f, r360_plane* out, int cap, in
     return 0;
 }
 
+extern "C" int r360_frame_get_local_planes(r360_frame* f, int sensor, r360_plane* out, int cap, int* n) {
+    if (int rc = ready(f)) return rc;
+    CHECK_ARG(f->local, "the frame was built without R360_BUILD_LOCAL_PLANES");
+    CHECK_ARG(sensor >= 0 && sensor < 8, "sensor out of range");
+    const auto& P = f->local->planes[sensor];
+    if (n) *n = int(P.size());
+    // x_rig = R x_sensor + t: directions go back by R^T, points by R^T (x - t), in double
+    const float* T = f->calib->rt[sensor];
+    auto back = [&](const P3& v, bool point, float* o) {
+        const double x = (double)v.x - (point ? T[12] : 0.f), y = (double)v.y - (point ? T[13] : 0.f), z = (double)v.z - (point ? T[14] : 0.f);
+        for (int k = 0; k < 3; ++k) o[k] = float((T[4 * k] * x + T[4 * k + 1] * y) + T[4 * k + 2] * z);
+    };
+    for (int i = 0; i < int(P.size()) && i < cap && out; ++i) {
+        const HPlane& p = P[i];
+        r360_plane& o = out[i];
+        back(p.normal, false, o.normal);
+        back(p.center, true, o.center);
+        back(p.ppal, false, o.ppal);
+        o.d = -float(((double)o.normal[0] * o.center[0] + (double)o.normal[1] * o.center[1]) + (double)o.normal[2] * o.center[2]);
+        o.area = p.area; o.elongation = p.elongation; o.curvature = p.curvature;
+        for (int k = 0; k < 3; ++k) o.nrgb[k] = p.nrgb[k];
+        o.intensity = p.intensity;
+        o.id = p.id; o.sensor = p.sensor; o.n_inliers = int(p.st.n); o.n_hull = int(p.hull.size());
+    }
+    return 0;
+}
+
+extern "C" int r360_frame_get_local_plane_labels(r360_frame* f, int sensor, int plane, int* labels, int cap, int* n) {
+    if (int rc = ready(f)) return rc;
+    CHECK_ARG(f->local, "the frame was built without R360_BUILD_LOCAL_PLANES");
+    CHECK_ARG(sensor >= 0 && sensor < 8 && n, "sensor out of range");
+    const auto& L = f->local->labels[sensor];
+    CHECK_ARG(plane >= 0 && plane < int(L.size()), "plane index out of range");
+    *n = int(L[plane].size());
+    for (int k = 0; k < *n && k < cap && labels; ++k) labels[k] = L[plane][k];
+    return 0;
+}
+
 extern "C" int r360_frame_get_plane_hull(r360_frame* f, int i, float* xyz, int cap, int* n) {
     if (int rc = ready(f)) return rc;
     const auto& P = f->pbmap->planes;
@@ -1728,6 +1785,8 @@ extern "C" int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const f
     P.ticket.reset();
     delete f->pbmap;
     f->pbmap = nullptr;
+    delete f->local;
+    f->local = nullptr;
     f->built = 0;   // the images are not the uploaded ones any more
     if (launch_segment_inputs(B, 1, G, st)) return -1;
     if (launch_segmentation(B, 1, G, st, ctx, nullptr)) return -1;
@@ -1869,6 +1928,8 @@ extern "C" int r360_frame_load_pbmap(r360_frame* f, const char* path) {
     f->pl.worker_rc = 0;
     delete f->pbmap;
     f->pbmap = pm;
+    delete f->local;
+    f->local = nullptr;
     f->built |= R360_BUILD_PLANES;
     return 0;
 }

@@ -799,8 +799,10 @@ extern "C" int r360_frame_build_async(r360_frame* f, unsigned flags) {
     if (flags & (R360_BUILD_CLOUD | R360_BUILD_PLANES)) {
         // buildSphereCloud + getPlanes (Frame360.h:467-510, 615-640): the per-pixel part is enqueued
         // here; the per-plane PbMap assembly runs on the host when the planes are first needed
+        f->want_local = (flags & R360_BUILD_LOCAL_PLANES) != 0;
         if (planes_enqueue(f)) return -1;
-        f->built |= R360_BUILD_CLOUD | R360_BUILD_PLANES;
+        f->built = (f->built & ~(unsigned)R360_BUILD_LOCAL_PLANES) | R360_BUILD_CLOUD | R360_BUILD_PLANES |
+                   (flags & R360_BUILD_LOCAL_PLANES);
         delete f->sphere_cloud;  // a cloud set by loadCloud is replaced by the built one
         f->sphere_cloud = nullptr;
     }

@@ -275,6 +275,7 @@ struct PlaneBufs {
     std::string worker_err;
 };
 struct PbMapHost;                    // host PbMap (host/pbmap.cpp)
+struct LocalPlanesHost;              // the sensors' planes before grouping (R360_BUILD_LOCAL_PLANES; host/pbmap.cpp)
 
 // One frame's plane-stage buffers as the plane kernels see them.  Every plane kernel takes a PlaneBatch (by value, in
 // the kernel-argument segment) and serves frame blockIdx.z of it (k_normals*: blockIdx.z / 8), so one launch runs
@@ -434,6 +435,35 @@ int launch_pgo_cgm(r360_ctx* ctx, const PgoDev& D, double lambda, double tol2, i
                    PgoCgState* d_state, PgoCgState* h_state, PgoOut* out);
 int launch_pgo_update(hipStream_t st, const PgoDev& D, const double* poses, const double* delta, double lambda,
                       double* trial, PgoOut* out);
+
+// ------------------------------------------------------------------ rig calibration (kernels/rigcal_kernels.hip, host/rigcal.cpp)
+constexpr int R360_RIGCAL_PAIRS = 28;   // (i, j), i < j, in the reference's map order
+constexpr int R360_RIGCAL_TPB = 256;    // rows per workgroup; a workgroup never spans two pairs
+constexpr int R360_RIGCAL_REC = 40;     // doubles per workgroup record: blocks ii, ij, jj (27), gradients i, j (6), four scalars
+constexpr int R360_RIGCAL_OUT = 21 * 21 + 21 + 4 + 1;   // H, g, the scalars, the cost-only weighted error
+// What the kernels read of one correspondence set: rebuilt when the rows change.
+struct RigcalDev {
+    int n = 0, nwg = 0;               // rows and workgroups of all pairs
+    const double* rows = nullptr;     // [n][10], the pairs back to back in pair order
+    const int* pair_start = nullptr;  // [29] first row of each pair
+    const int* wg_start = nullptr;    // [29] first workgroup of each pair
+    const int* wg_pair = nullptr;     // [nwg] the workgroup's pair
+    double* rec = nullptr;            // [nwg][R360_RIGCAL_REC]
+    double* out = nullptr;            // [R360_RIGCAL_OUT]
+};
+// rot: [2][8][9] row-major rotations, the current set and the trial set.  mode 0 rotation, 1 translation.  The
+// cost-only form reads the trial set and writes out[R360_RIGCAL_OUT - 1] alone.
+int launch_rigcal_accum(hipStream_t st, const RigcalDev& D, const double* rot, int mode, bool weighted, bool cost_only);
+struct RigcalTrimParams { double dist, degenerate; int max_redraws; };
+// trials [trial0, trial0 + n) of one pair's rows [m][10]: counts[n], flags[n] (1: no non-degenerate draw)
+int launch_rigcal_ransac(hipStream_t st, const double* rows, int m, unsigned seed, int trial0, int n,
+                         const RigcalTrimParams& p, int* counts, int* flags);
+// the inlier mask [m] of one trial
+int launch_rigcal_mask(hipStream_t st, const double* rows, int m, unsigned seed, int trial, const RigcalTrimParams& p,
+                       unsigned char* mask);
+
+// per key {sensor, label}: out = {pixels of the sensor's [h][w] label image with that label, sum of (row + col) over them}
+int launch_rigcal_pixsum(hipStream_t st, const int* labf, int w, int h, const int2* keys, int n_keys, longlong2* out);
 
 // ------------------------------------------------------------------ host objects
 struct r360_plane_queue;
@@ -624,6 +654,8 @@ struct r360_frame {
     std::atomic<unsigned> built{0};
     PlaneBufs pl;
     PbMapHost* pbmap = nullptr;
+    LocalPlanesHost* local = nullptr;  // kept by a build with R360_BUILD_LOCAL_PLANES, else null
+    bool want_local = false;           // the next plane assembly keeps them (set by the build, taken by planes_spawn_assembly)
     uint64_t timestamp = 0;            // Frame360::timeStamp (Frame360.h:181-184)
     unsigned compacted = 0;            // bit l: lv[l].pts / d_npts[l] hold level l's compacted source points
     // the pyramid build compacts every level: a lone alignment's passes (PF 5) read the compacted points.  Frames that
