@@ -14,7 +14,12 @@
 // At the end: the chained and the optimised keyframe poses, in synthetic mode each one's distance from the path
 // (r360_synth_path_pose), and the global map fused twice (r360_ctx_map_add_frame), at the chained and at the
 // optimised poses, with both sizes.
-//   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o]
+// With --submaps the topological map of KFsphere_SLAM.cpp goes along (r360::Map360 / TopologicalMap360): every keyframe
+// joins the current area, every accepted tracking or loop connection enters the SSO table with align360.SSO (:402,
+// :443, :613-628), Partitioner() runs when the keyframe's index in its area is a multiple of 4 (:710-717) and the
+// "Places" lines follow (:733-740); at the end a line per area gives its keyframes and its representative.  Without
+// the flag nothing of this runs or prints.
+//   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]
 //          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
 //          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
 #include <rgbd360/rgbd360.h>
@@ -50,12 +55,13 @@ int main(int argc, char** argv) {
     float kf_dist = 0.4f;
     std::string save, frames_arg;
     int n_synth = 0;
-    bool synthetic = false;
+    bool synthetic = false, submaps = false;
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
         if (a == "--min-gap" && k + 1 < argc) min_gap = std::atoi(argv[++k]);
         else if (a == "--kf-dist" && k + 1 < argc) kf_dist = float(std::atof(argv[++k]));
         else if (a == "--save" && k + 1 < argc) save = argv[++k];
+        else if (a == "--submaps") submaps = true;
         else if (a == "--synthetic-frames" && k + 1 < argc) { frames_arg = argv[++k]; synthetic = true; }
         else if (a == "--synthetic" && k + 1 < argc) { n_synth = std::atoi(argv[++k]); synthetic = true; }
         else pos.push_back(a);
@@ -70,7 +76,7 @@ int main(int argc, char** argv) {
     for (int k = 0; k < n_synth && frames_arg.empty(); ++k) order.push_back(k);
     if ((synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
         std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
-                             "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o]\n", argv[0]);
+                             "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n", argv[0]);
         return 1;
     }
     const std::string dir = synthetic ? "" : pos[0];
@@ -139,6 +145,14 @@ int main(int argc, char** argv) {
         chainPose.push_back(currentPose);
         vOptimizedPoses.push_back(currentPose);
         std::printf("Added vertex: %d\n", optimizer.addVertex(currentPose.cast<double>()));
+        // KFsphere_SLAM.cpp:259-260, 330-337: the map and its topological arrangement
+        r360::Map360 Map;
+        std::unique_ptr<r360::TopologicalMap360> topologicalMap;
+        if (submaps) {
+            topologicalMap.reset(new r360::TopologicalMap360(Map, ctx));
+            Map.vpSpheres.push_back(kfs.back().get());
+            topologicalMap->addKeyframe(Map.currentArea);
+        }
         Matrix4f rigidTransf_dense_ref = Matrix4f::Identity();
         int loops = 0, optimisations = 0;
         double F_first = 0.0, F_last = 0.0;
@@ -161,6 +175,7 @@ int main(int argc, char** argv) {
             rigidTransf_dense_ref = align360.getOptimalPose();
             Matrix4f rigidTransf_dense = rotOffsetInv * rigidTransf_dense_ref * rotOffset;
             const r360::Matrix6f hessian = align360.getHessian();
+            const float candidateKF_sso = align360.SSO;  // :402
             const float dist = translationNorm(rigidTransf_dense);
             std::printf("frame %d: PbMap %s matches %zu area %.3f; dense %s dist %.3f residuals %.5f %.5f\n", id,
                         bGoodTracking ? "ok" : "failed", trackedMatches, trackedArea, ok ? "ok" : "ILL-POSED", dist,
@@ -184,6 +199,14 @@ int main(int argc, char** argv) {
             vOptimizedPoses.push_back(currentPose);
             rigidTransf_dense_ref = Matrix4f::Identity();
             r360::Frame360* newKF = kfs.back().get();
+            int newLocalFrameID = 0;
+            if (submaps) {                               // :566-615
+                newLocalFrameID = int(Map.vsAreas[Map.currentArea].size());
+                Map.vpSpheres.push_back(newKF);
+                topologicalMap->addKeyframe(Map.currentArea);
+                topologicalMap->addConnection(unsigned(newFrameID), unsigned(nearestKF), candidateKF_sso);
+                std::printf("SSO is %.6f\n", candidateKF_sso);
+            }
 
             // loop closure against the earlier keyframes (LoopClosure360.h:290-321)
             bool bHasNewLC = false;
@@ -208,6 +231,7 @@ int main(int argc, char** argv) {
                 if (lok && (!occlusion || align360.avDepthResidual < 2.0)) {
                     optimizer.addEdge(compareLocalIdx, newFrameID, relativePose.cast<double>(), informationMatrix.cast<double>());
                     std::printf("LC Add edge between %d and %d (residual %.5f)\n", compareLocalIdx, newFrameID, align360.avDepthResidual);
+                    if (submaps) topologicalMap->addConnection(unsigned(newFrameID), unsigned(compareLocalIdx), align360.SSO);   // :628
                     bHasNewLC = true;
                     ++loops;
                 }
@@ -222,7 +246,22 @@ int main(int argc, char** argv) {
                 std::printf("Optimize graph SLAM %zu: status %d iterations %d cost %.9g -> %.9g\n", kfs.size(), st.status, st.iterations,
                             st.F_initial, st.F_final);
             }
+            if (submaps && newLocalFrameID % 4 == 0) {   // Visibility division (Normalized-cut), :710-740
+                topologicalMap->Partitioner();
+                std::printf("\tPlaces\n");
+                for (size_t node = 0; node < Map.vsNeighborAreas.size(); ++node) {
+                    std::printf("\t%zu:", node);
+                    for (unsigned nb : Map.vsNeighborAreas[node]) std::printf(" %u", nb);
+                    std::printf("\n");
+                }
+            }
         }
+        if (submaps)
+            for (size_t node = 0; node < Map.vsAreas.size(); ++node) {
+                std::printf("area %zu: keyframes", node);
+                for (unsigned k : Map.vsAreas[node]) std::printf(" %u", k);
+                std::printf(" representative %u%s\n", Map.vSelectedKFs[node], node == Map.currentArea ? " current" : "");
+            }
 
         std::printf("%zu keyframes, %d loop edges, %d optimisations", kfs.size(), loops, optimisations);
         if (optimisations) std::printf(", cost %.9g -> %.9g", F_first, F_last);

@@ -4,7 +4,8 @@
 // succeeds (:169-231).  The candidates of a frame are registered at once on a BatchRegistration; the winner is
 // the one the sequential loop would pick.  Every `lc_every` keyframes, the newest keyframe is checked against
 // the older keyframes closer than 5 m (LoopClosure360.h:291-298) in one batched call with the PbMap gate and
-// alignFrames360 refinement.  Graph optimisation, submaps and the viewer are out of scope.
+// alignFrames360 refinement.  Graph optimisation and the submaps are apps/KFsphereSLAM.cpp's part (r360::GraphOptimizer,
+// r360::TopologicalMap360 with --submaps, r360::Relocalizer360); the viewer is out of scope.
 //   usage: SphereGraphTracking <dir with sphere_images_<n>.bin> [first] [step] [calib_dir]
 //          SphereGraphTracking --synthetic <n_frames>        (procedural room, 8 x 480x640, no I/O)
 //   either form may end in "--map FILE.pcd": the keyframes' clouds are fused into the context's device-resident

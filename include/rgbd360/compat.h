@@ -21,7 +21,8 @@
 //   * mrpt::format (printf-style std::string) unless MRPT's own header came first;
 //   * PROJECT_SOURCE_PATH = r360_data_dir() (data/) unless the build defines it, so the reference's
 //     "%s/config_files/..." paths resolve to data/config_files/...;
-//   * PI and fexists() of Miscellaneous.h (:44, :120-124).
+//   * PI and fexists() of Miscellaneous.h (:44, :120-124);
+//   * with RGBD360_COMPAT_MAP360 defined first: Map360, TopologicalMap360 and Relocalizer360.
 #pragma once
 #include <rgbd360/rgbd360.h>
 
@@ -40,6 +41,13 @@ using r360::PbMap;
 using r360::Plane;
 using r360::RegisterPhotoICP;
 using r360::RegisterRGBD360;
+// Map360.h / TopologicalMap360.h / Relocalizer360.h: opt-in, since call-site files written before these classes
+// existed declare a reduced Map360 of their own
+#ifdef RGBD360_COMPAT_MAP360
+using r360::Map360;
+using r360::Relocalizer360;
+using r360::TopologicalMap360;
+#endif
 
 #if !defined(RGBD360_WITH_EIGEN) && !defined(EIGEN_CORE_H) && !defined(EIGEN_CORE_MODULE_H)
 namespace r360 {

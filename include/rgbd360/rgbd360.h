@@ -44,6 +44,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -1166,6 +1167,147 @@ class Calibration {
     r360_rigcal* h_ = nullptr;
     double est_[128];
     bool specs_loaded_ = false;
+};
+
+// ------------------------------------------------------------------ Map360 / TopologicalMap360 / Relocalizer360
+// Map360 (include/Map360.h:41-97): the pose graph of keyframes and its arrangement in topological areas.  The
+// members are the reference's; TopologicalMap360 keeps vsAreas, vsNeighborAreas, vSelectedKFs, currentArea and every
+// frame's node up to date after each of its calls.
+class Map360 {
+  public:
+    std::vector<Frame360*> vpSpheres;
+    std::vector<Matrix4f> vTrajectoryPoses;
+    std::vector<Matrix4f> vOptimizedPoses;
+    std::vector<float> vTrajectoryIncrements;
+    std::map<unsigned, std::map<unsigned, std::pair<Matrix4f, Matrix6f> > > mmConnectionKFs;
+    unsigned currentArea = 0;
+    std::vector<std::set<unsigned> > vsAreas;
+    std::vector<std::set<unsigned> > vsNeighborAreas;
+    std::vector<unsigned> vSelectedKFs;
+    std::mutex mapMutex;
+    void addKeyframe(Frame360* sphere, Matrix4f& pose) {
+        sphere->pose = pose;
+        vpSpheres.push_back(sphere);
+        vTrajectoryPoses.push_back(pose);
+        vOptimizedPoses.push_back(pose);
+    }
+};
+
+// TopologicalMap360 (include/TopologicalMap360.h) over r360_topomap_*: the SSO lives in one table keyed by global
+// keyframe ids, so the reference's direct writes into vSSO[area](i, j) (KFsphere_SLAM.cpp:613, SphereGraphSLAM.cpp:
+// 165-166, 215) become addKeyframe() / addConnection() calls.  addKeyframe() follows Map.addKeyframe() of the same
+// keyframe; Partitioner() is RecursiveSpectralPartition(SSO, parts, 0.8, false, true, true, 3) on the GPU.
+class TopologicalMap360 {
+  public:
+    explicit TopologicalMap360(Map360& map) : Map(map), keep_(default_context_ptr()) {
+        check(r360_topomap_create(keep_->get(), &h_), "r360_topomap_create");
+        sync();
+    }
+    TopologicalMap360(Map360& map, Context& ctx) : Map(map) {
+        check(r360_topomap_create(ctx.get(), &h_), "r360_topomap_create");
+        sync();
+    }
+    ~TopologicalMap360() { r360_topomap_destroy(h_); }
+    TopologicalMap360(const TopologicalMap360&) = delete;
+    TopologicalMap360& operator=(const TopologicalMap360&) = delete;
+    r360_topo_params& params() { return params_; }
+    // the newest keyframe of Map.vpSpheres joins the current area (the argument is the reference's, :81)
+    void addKeyframe(unsigned /*currentArea*/ = 0) {
+        check(r360_topomap_add_keyframe(h_, nullptr), "TopologicalMap360::addKeyframe");
+        sync();
+    }
+    // the not-registered branch (SphereGraphSLAM.cpp:232-242): forget the newest keyframe
+    void dropLastKeyframe() {
+        check(r360_topomap_drop_last(h_), "TopologicalMap360::dropLastKeyframe");
+        sync();
+    }
+    void addConnection(unsigned kf1_global, unsigned kf2_global, const float& sso) {
+        check(r360_topomap_add_connection(h_, int(kf1_global), int(kf2_global), sso), "TopologicalMap360::addConnection");
+        sync();
+    }
+    // the SSO matrix [n][n] (row-major) of the current area's vicinity; vicinityKFs: its keyframes in matrix order
+    std::vector<float> getVicinitySSO(std::vector<unsigned>* vicinityKFs = nullptr) {
+        int n = 0;
+        check(r360_topomap_vicinity(h_, nullptr, nullptr, 0, &n), "getVicinitySSO");
+        std::vector<int> ids(std::max(n, 1));
+        std::vector<float> sso(size_t(std::max(n, 1)) * std::max(n, 1));
+        check(r360_topomap_vicinity(h_, ids.data(), sso.data(), n, &n), "getVicinitySSO");
+        sso.resize(size_t(n) * n);
+        if (vicinityKFs) vicinityKFs->assign(ids.begin(), ids.begin() + n);
+        return sso;
+    }
+    // returns the number of new areas
+    int Partitioner() {
+        int k = 0;
+        check(r360_topomap_partition(h_, &params_, &k), "TopologicalMap360::Partitioner");
+        sync();
+        return k;
+    }
+    r360_topomap* get() const { return h_; }
+
+  private:
+    void sync() {
+        int n = 0, na = 0, cur = 0;
+        check(r360_topomap_areas(h_, nullptr, 0, &n, &na, &cur), "r360_topomap_areas");
+        std::vector<int> area(std::max(n, 1));
+        check(r360_topomap_areas(h_, area.data(), n, &n, &na, &cur), "r360_topomap_areas");
+        Map.currentArea = unsigned(cur);
+        Map.vsAreas.assign(na, std::set<unsigned>());
+        Map.vsNeighborAreas.assign(na, std::set<unsigned>());
+        Map.vSelectedKFs.assign(na, 0u);
+        for (int k = 0; k < n; ++k) {
+            Map.vsAreas[area[k]].insert(unsigned(k));
+            if (size_t(k) < Map.vpSpheres.size() && Map.vpSpheres[k]) Map.vpSpheres[k]->node = unsigned(area[k]);
+        }
+        std::vector<int> nb(std::max(na, 1));
+        for (int a = 0; a < na; ++a) {
+            int m = 0, kf = -1;
+            check(r360_topomap_neighbors(h_, a, nb.data(), na, &m), "r360_topomap_neighbors");
+            Map.vsNeighborAreas[a].insert(nb.begin(), nb.begin() + m);
+            check(r360_topomap_selected(h_, a, &kf), "r360_topomap_selected");
+            Map.vSelectedKFs[a] = kf < 0 ? 0u : unsigned(kf);
+        }
+    }
+    Map360& Map;
+    std::shared_ptr<Context> keep_;     // the default context, when that is the one in use
+    r360_topomap* h_ = nullptr;
+    r360_topo_params params_ = default_params();
+    static r360_topo_params default_params() {
+        r360_topo_params p;
+        r360_topo_default_params(&p);
+        return p;
+    }
+};
+
+// Relocalizer360 (include/Relocalizer360.h:43-94) over r360_relocalize: the keyframes of Map.vpSpheres, newest first,
+// registered with the frame by PbMap under PLANAR_3DoF in chunks of the batch's lanes.
+class Relocalizer360 {
+  public:
+    explicit Relocalizer360(Map360& map, int lanes = 4) : registerer(default_device(), lanes), Map(map) {}
+    BatchRegistration registerer;
+    unsigned relocKF = 0;
+    Matrix4d rigidTransf;
+    Matrix6d informationM;
+    size_t max_match_planes = 25;
+    // the frame with respect to which the system has relocalised, or -1
+    int relocalize(Frame360* currentFrame) {
+        std::vector<r360_frame*> kfs;
+        for (auto f : Map.vpSpheres) kfs.push_back(f->get());
+        int kf = -1;
+        Matrix4d pose;
+        Matrix6d info;
+        check(r360_relocalize(registerer.get(), kfs.data(), int(kfs.size()), currentFrame->get(), max_match_planes, 5, 10.f,
+                              &kf, pose.data(), info.data()),
+              "Relocalizer360::relocalize");
+        if (kf < 0) return -1;
+        relocKF = unsigned(kf);
+        rigidTransf = pose;
+        informationM = info;
+        return kf;
+    }
+
+  private:
+    Map360& Map;
 };
 
 }  // namespace r360

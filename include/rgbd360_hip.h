@@ -923,6 +923,77 @@ int  r360_rigcal_eval(r360_rigcal* h, int mode, int weighted, double* H, double*
 int  r360_rigcal_ransac_eval(r360_rigcal* h, int i, int j, const r360_rigcal_trim_params* params, unsigned seed,
                              int trial0, int n, int* counts, int* flags);
 
+/* ---- Topological submaps: the SSO graph and its spectral partition (include/Map360.h, TopologicalMap360.h,
+ * Relocalizer360.h; statement: tests/topo_model.py).
+ *
+ * A graph is a symmetric n x n matrix A of fp32 sensed-space-overlap values, row-major, >= 0, zero diagonal,
+ * 1 <= n <= R360_TOPO_MAX_NODES.  bisect: the Fiedler vector v of the plain Laplacian diag(row sums) - A (cyclic Jacobi
+ * in fp64, sweeps until off(L) <= 1e-14 ||L||_F), side 1 = {i : v_i >= mean(v)}, side 2 the rest ({i <= n/2} and
+ * the rest when one would be empty), cut = the normalised cut of the two sides.  partition
+ * (mrpt::graphs::CGraphPartitioner::RecursiveSpectralPartition, TopologicalMap360.h:411): a cluster whose cut is above
+ * threshold_ncut, or one of whose sides has fewer than min_cluster nodes, stays one part; otherwise its sides are
+ * partitioned in turn (recursive) or are the two parts; parts are numbered by their first node (RearrangePartition,
+ * :372-387).  One workgroup per cluster, one launch per recursion level for all graphs of a call; results are
+ * identical bit for bit between runs and between a lone and a batched call.
+ * Return values: 0; R360_TOPO_NOT_CONVERGED (results written) when a cluster's Jacobi sweeps ran out; R360_EINVAL for
+ * n < 1, n > R360_TOPO_MAX_NODES, a non-finite, negative or asymmetric entry, a non-zero diagonal or bad parameters
+ * (nothing is launched; the context stays usable). */
+#define R360_TOPO_MAX_NODES 256
+#define R360_TOPO_NOT_CONVERGED 1
+typedef struct {
+    double threshold_ncut;   /* 0.8 */
+    int min_cluster;         /* 3; at least 1 */
+    int recursive;           /* 1 */
+} r360_topo_params;
+void r360_topo_default_params(r360_topo_params* p);
+/* Parity hook: one bisection.  side [n]: 1 or 2; eigenvalues [n] ascending and fiedler [n] may be NULL; sweeps: the
+ * Jacobi sweeps done. */
+int  r360_topo_bisect(r360_ctx* ctx, const float* A, int n, int* side, double* cut, double* eigenvalues, double* fiedler,
+                      int* sweeps);
+/* part_of [n]; cuts (may be NULL, 2 n - 1 entries at most): the cut of every bisection made, ordered by the bisected
+ * cluster's lowest node, of nested clusters the larger first (an order that does not depend on the eigenvectors'
+ * signs); n_bisections (may be NULL) their number. */
+int  r360_topo_partition(r360_ctx* ctx, const float* A, int n, const r360_topo_params* params, int* part_of, int* n_parts,
+                         double* cuts, int* n_bisections);
+int  r360_topo_partition_batch(r360_ctx* ctx, int count, const float* const* A, const int* n,
+                               const r360_topo_params* params, int* const* part_of, int* n_parts);
+
+/* The bookkeeping of Map360 + TopologicalMap360 on the host: keyframes (global ids 0, 1, ...) with an area each, one
+ * symmetric SSO table over keyframe ids, the current area.  Two areas are neighbours exactly when a positive SSO joins
+ * two of their keyframes; an area neighbours itself.  An area's representative keyframe (vSelectedKFs) has the
+ * largest sum of SSO to the area's other keyframes, the lowest id among equals.
+ *   add_keyframe    the new keyframe joins the current area; *kf (may be NULL) = its id
+ *   drop_last       undoes the last add_keyframe and that keyframe's connections (SphereGraphSLAM.cpp:232-242)
+ *   add_connection  sets SSO(kf1, kf2) = SSO(kf2, kf1) = sso, within one area or across two (TopologicalMap360.h:107-131)
+ *   vicinity        the keyframes of the current area's neighbours (itself included), areas ascending, ids ascending
+ *                   inside an area, and their SSO matrix [n][n]; kf_ids / sso may be NULL (count only); -4 when cap < n
+ *   partition       Partitioner(): cuts the vicinity's matrix.  Nothing happens with fewer than 3 keyframes or when the
+ *                   parts are no more than the vicinity's areas; otherwise those areas, ascending, take the first
+ *                   parts, *n_new_areas new areas the others, and the current area is the one of the newest keyframe
+ *   areas           area_of [cap] (may be NULL), the counts and the current area
+ *   neighbors       the area's neighbours ascending; out may be NULL
+ *   selected        the area's representative keyframe, -1 for an empty area
+ * Only partition uses the context, which must live until the last partition call; destroy never reads it. */
+typedef struct r360_topomap r360_topomap;
+int  r360_topomap_create(r360_ctx* ctx, r360_topomap** out);
+void r360_topomap_destroy(r360_topomap* m);
+int  r360_topomap_add_keyframe(r360_topomap* m, int* kf);
+int  r360_topomap_drop_last(r360_topomap* m);
+int  r360_topomap_add_connection(r360_topomap* m, int kf1, int kf2, float sso);
+int  r360_topomap_vicinity(r360_topomap* m, int* kf_ids, float* sso, int cap, int* n);
+int  r360_topomap_partition(r360_topomap* m, const r360_topo_params* params, int* n_new_areas);
+int  r360_topomap_areas(const r360_topomap* m, int* area_of, int cap, int* n_kf, int* n_areas, int* current_area);
+int  r360_topomap_neighbors(const r360_topomap* m, int area, int* out, int cap, int* n);
+int  r360_topomap_selected(const r360_topomap* m, int area, int* kf);
+
+/* Relocalizer360::relocalize (include/Relocalizer360.h:78-93): RegisterPbMap(kfs[i], frame, max_match_planes,
+ * PLANAR_3DoF) for i = n_kf - 1, ..., 0; the first keyframe in that order registered with at least min_matches (5)
+ * matched planes and more than min_area (10) m2 of matched area wins: *kf = its index, pose [16] and info [36] (may be
+ * NULL) = getPose() / getInfoMat() as doubles, layouts as r360_pair_result's.  *kf = -1 when there is none.  Candidates run in
+ * chunks of the batch's lanes through r360_batch_register, newest first; later chunks are not run once one wins. */
+int  r360_relocalize(r360_batch* b, r360_frame* const* kfs, int n_kf, r360_frame* frame, size_t max_match_planes,
+                     int min_matches, float min_area, int* kf, double* pose, double* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ __all__ = [
     "GicpParams", "GicpStats", "GeneralizedICP", "GraphParams", "GraphStats", "PoseGraph", "g2o_write", "g2o_read",
     "PHOTO_CONSISTENCY", "DEPTH_CONSISTENCY", "PHOTO_DEPTH", "synth_path_pose", "exp_se3",
     "LIB_PATH", "ABI_SYMBOLS", "Batch", "PairJob", "PairResult", "JOB_PBMAP_ONLY", "JOB_GATED", "JOB_ALWAYS",
+    "TopoParams", "TopologicalMap", "Relocalizer", "topo_bisect", "topo_partition", "topo_partition_batch",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,6 +108,23 @@ class GraphStats(C.Structure):
 
 
 GRAPH_CONVERGED, GRAPH_ITERATION_LIMIT, GRAPH_STALLED, GRAPH_CG_NOT_CONVERGED = 0, 1, 2, 3
+
+
+class TopoParams(C.Structure):
+    """r360_topo_params — the spectral partition's settings (see include/rgbd360_hip.h)."""
+    _fields_ = [("threshold_ncut", C.c_double), ("min_cluster", C.c_int), ("recursive", C.c_int)]
+
+    @classmethod
+    def default(cls, **kw) -> "TopoParams":
+        p = cls()
+        lib().r360_topo_default_params(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+
+TOPO_MAX_NODES = 256
+TOPO_LDS_MAX_NODES = 96   # up to here a cluster's matrices live in LDS, above in the context's scratch
 
 
 class RigcalStats(C.Structure):
@@ -454,6 +472,23 @@ _SIGS = [
     ("r360_frame_get_local_plane_labels", C.c_int, [_P, C.c_int, C.c_int, _IP, C.c_int, _IP]),
     ("r360_rigcal_ransac_eval", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(RigcalTrimParams), C.c_uint, C.c_int, C.c_int,
                                           _IP, _IP]),
+    ("r360_topo_default_params", None, [C.POINTER(TopoParams)]),
+    ("r360_topo_bisect", C.c_int, [_P, _FP, C.c_int, _IP, _DP, _DP, _DP, _IP]),
+    ("r360_topo_partition", C.c_int, [_P, _FP, C.c_int, C.POINTER(TopoParams), _IP, _IP, _DP, _IP]),
+    ("r360_topo_partition_batch", C.c_int, [_P, C.c_int, C.POINTER(_FP), _IP, C.POINTER(TopoParams), C.POINTER(_IP),
+                                            _IP]),
+    ("r360_topomap_create", C.c_int, [_P, C.POINTER(_P)]),
+    ("r360_topomap_destroy", None, [_P]),
+    ("r360_topomap_add_keyframe", C.c_int, [_P, _IP]),
+    ("r360_topomap_drop_last", C.c_int, [_P]),
+    ("r360_topomap_add_connection", C.c_int, [_P, C.c_int, C.c_int, C.c_float]),
+    ("r360_topomap_vicinity", C.c_int, [_P, _IP, _FP, C.c_int, _IP]),
+    ("r360_topomap_partition", C.c_int, [_P, C.POINTER(TopoParams), _IP]),
+    ("r360_topomap_areas", C.c_int, [_P, _IP, C.c_int, _IP, _IP, _IP]),
+    ("r360_topomap_neighbors", C.c_int, [_P, C.c_int, _IP, C.c_int, _IP]),
+    ("r360_topomap_selected", C.c_int, [_P, C.c_int, _IP]),
+    ("r360_relocalize", C.c_int, [_P, C.POINTER(C.c_void_p), C.c_int, _P, C.c_size_t, C.c_int, C.c_float, _IP, _DP,
+                                  _DP]),
 ]
 ABI_SYMBOLS = [s[0] for s in _SIGS]
 
@@ -2021,3 +2056,148 @@ class RigCalibration:
         _check(lib().r360_rigcal_ransac_eval(self.h, i, j, C.byref(p), seed, trial0, n, counts.ctypes.data_as(_IP),
                                              flags.ctypes.data_as(_IP)), "rigcal_ransac_eval")
         return counts, flags
+
+
+def _topo_matrix(A) -> np.ndarray:
+    A = np.ascontiguousarray(A, np.float32)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("a square matrix is expected")
+    return A
+
+
+def topo_bisect(ctx: "Context", A):
+    """r360_topo_bisect: one spectral bisection of the SSO graph A [n, n] ->
+    dict(side [n] (1 / 2), cut, eigenvalues [n] ascending, fiedler [n], sweeps, converged)."""
+    A = _topo_matrix(A)
+    n = A.shape[0]
+    side = np.zeros(max(n, 1), np.int32)
+    ev, fv = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    cut, sweeps = C.c_double(), C.c_int()
+    rc = _check(lib().r360_topo_bisect(ctx.h, _fptr(A), n, side.ctypes.data_as(_IP), C.byref(cut), _dptr(ev), _dptr(fv),
+                                       C.byref(sweeps)), "topo_bisect")
+    return dict(side=side[:n], cut=cut.value, eigenvalues=ev[:n], fiedler=fv[:n], sweeps=sweeps.value, converged=rc == 0)
+
+
+def topo_partition(ctx: "Context", A, params: "TopoParams | None" = None, return_cuts: bool = False):
+    """r360_topo_partition (RecursiveSpectralPartition, TopologicalMap360.h:411) -> part_of [n], the parts numbered by
+    their first node; with return_cuts also the cut of every bisection (by the cluster's lowest node, larger first)."""
+    A = _topo_matrix(A)
+    n = A.shape[0]
+    part = np.zeros(max(n, 1), np.int32)
+    cuts = np.zeros(2 * max(n, 1))
+    n_parts, n_bis = C.c_int(), C.c_int()
+    _check(lib().r360_topo_partition(ctx.h, _fptr(A), n, None if params is None else C.byref(params),
+                                     part.ctypes.data_as(_IP), C.byref(n_parts), _dptr(cuts), C.byref(n_bis)),
+           "topo_partition")
+    return (part[:n], cuts[:n_bis.value].copy()) if return_cuts else part[:n]
+
+
+def topo_partition_batch(ctx: "Context", graphs, params: "TopoParams | None" = None):
+    """r360_topo_partition_batch: every graph's part_of, all graphs' clusters of one recursion level in one launch."""
+    mats = [_topo_matrix(A) for A in graphs]
+    count = len(mats)
+    ns = np.array([A.shape[0] for A in mats] or [0], np.int32)
+    parts = [np.zeros(max(A.shape[0], 1), np.int32) for A in mats]
+    ap = (_FP * max(count, 1))(*[_fptr(A) for A in mats])
+    pp = (_IP * max(count, 1))(*[p.ctypes.data_as(_IP) for p in parts])
+    n_parts = np.zeros(max(count, 1), np.int32)
+    _check(lib().r360_topo_partition_batch(ctx.h, count, ap, ns.ctypes.data_as(_IP),
+                                           None if params is None else C.byref(params), pp,
+                                           n_parts.ctypes.data_as(_IP)), "topo_partition_batch")
+    return [p[:A.shape[0]] for p, A in zip(parts, mats)]
+
+
+class TopologicalMap:
+    """The bookkeeping of Map360 + TopologicalMap360 (r360_topomap_*): keyframes with an area each, one SSO table, the
+    current area; Partitioner() cuts the current area's vicinity on the GPU."""
+
+    def __init__(self, ctx: "Context"):
+        h = C.c_void_p()
+        _check(lib().r360_topomap_create(ctx.h, C.byref(h)), "r360_topomap_create")
+        self.h = h
+        self.ctx = ctx
+
+    def close(self):
+        if self.h:
+            lib().r360_topomap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def addKeyframe(self) -> int:
+        kf = C.c_int()
+        _check(lib().r360_topomap_add_keyframe(self.h, C.byref(kf)), "topomap_add_keyframe")
+        return kf.value
+
+    def dropLast(self):
+        _check(lib().r360_topomap_drop_last(self.h), "topomap_drop_last")
+
+    def addConnection(self, kf1: int, kf2: int, sso: float):
+        _check(lib().r360_topomap_add_connection(self.h, kf1, kf2, sso), "topomap_add_connection")
+
+    def getVicinitySSO(self):
+        """(keyframe ids [n], SSO [n, n]) of the current area and its neighbours."""
+        n = C.c_int()
+        _check(lib().r360_topomap_vicinity(self.h, None, None, 0, C.byref(n)), "topomap_vicinity")
+        ids, A = np.zeros(max(n.value, 1), np.int32), np.zeros(max(n.value, 1) ** 2, np.float32)
+        _check(lib().r360_topomap_vicinity(self.h, ids.ctypes.data_as(_IP), _fptr(A), n.value, C.byref(n)),
+               "topomap_vicinity")
+        return ids[:n.value], A[:n.value * n.value].reshape(n.value, n.value)
+
+    def Partitioner(self, params: "TopoParams | None" = None) -> int:
+        """Returns the number of new areas."""
+        k = C.c_int()
+        _check(lib().r360_topomap_partition(self.h, None if params is None else C.byref(params), C.byref(k)),
+               "topomap_partition")
+        return k.value
+
+    def areas(self):
+        """(area_of [n_kf], n_areas, current_area)."""
+        n, na, cur = C.c_int(), C.c_int(), C.c_int()
+        _check(lib().r360_topomap_areas(self.h, None, 0, C.byref(n), C.byref(na), C.byref(cur)), "topomap_areas")
+        a = np.zeros(max(n.value, 1), np.int32)
+        _check(lib().r360_topomap_areas(self.h, a.ctypes.data_as(_IP), n.value, C.byref(n), C.byref(na), C.byref(cur)),
+               "topomap_areas")
+        return a[:n.value], na.value, cur.value
+
+    def neighbors(self, area: int) -> list:
+        n = C.c_int()
+        _check(lib().r360_topomap_neighbors(self.h, area, None, 0, C.byref(n)), "topomap_neighbors")
+        out = np.zeros(max(n.value, 1), np.int32)
+        _check(lib().r360_topomap_neighbors(self.h, area, out.ctypes.data_as(_IP), n.value, C.byref(n)),
+               "topomap_neighbors")
+        return [int(v) for v in out[:n.value]]
+
+    def selected(self, area: int) -> int:
+        kf = C.c_int()
+        _check(lib().r360_topomap_selected(self.h, area, C.byref(kf)), "topomap_selected")
+        return kf.value
+
+
+class Relocalizer:
+    """Relocalizer360 (include/Relocalizer360.h:43-94) over r360_relocalize: the newest keyframe that registers with
+    the frame by PbMap under PLANAR_3DoF with enough matched planes and area."""
+
+    def __init__(self, batch: "Batch", max_match_planes: int = 25, min_matches: int = 5, min_area: float = 10.0):
+        self.batch = batch
+        self.max_match_planes, self.min_matches, self.min_area = max_match_planes, min_matches, min_area
+        self.relocKF = -1
+        self.rigidTransf = np.eye(4)
+        self.informationM = np.zeros((6, 6))
+
+    def relocalize(self, keyframes, frame) -> int:
+        kfs = list(keyframes)
+        ptrs = (C.c_void_p * max(1, len(kfs)))(*[k.h.value for k in kfs])
+        pose, info = np.zeros(16), np.zeros(36)
+        kf = C.c_int()
+        _check(lib().r360_relocalize(self.batch.h, ptrs, len(kfs), frame.h, self.max_match_planes, self.min_matches,
+                                     self.min_area, C.byref(kf), _dptr(pose), _dptr(info)), "r360_relocalize")
+        if kf.value >= 0:
+            self.relocKF = kf.value
+            self.rigidTransf = _from16(pose)
+            self.informationM = info.reshape(6, 6).T.copy()
+        return kf.value

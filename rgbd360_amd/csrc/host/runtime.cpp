@@ -309,6 +309,7 @@ extern "C" void r360_ctx_destroy(r360_ctx* c) {
     for (auto& s : c->bvox) vox_slot_free(s);
     map_state_free(c->vmap);   // voxel-filter scratch and the context's global map
     gicp_state_free(c->gicp);  // Generalized-ICP clouds and pass buffers
+    topo_state_free(c->topo);  // spectral partitioning buffers
     hipHostFree(c->h_unary); hipHostFree(c->h_bin);
     if (c->up_stream) {
         hipStreamSynchronize(c->up_stream);

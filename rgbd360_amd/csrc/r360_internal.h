@@ -465,12 +465,63 @@ int launch_rigcal_mask(hipStream_t st, const double* rows, int m, unsigned seed,
 // per key {sensor, label}: out = {pixels of the sensor's [h][w] label image with that label, sum of (row + col) over them}
 int launch_rigcal_pixsum(hipStream_t st, const int* labf, int w, int h, const int2* keys, int n_keys, longlong2* out);
 
+// ------------------------------------------------------------------ topological submaps (kernels/topo_kernels.hip, host/topo.cpp)
+constexpr int R360_TOPO_TPB = 1024;            // one workgroup per pending cluster
+constexpr int R360_TOPO_LDS_MAX_NODES = 96;    // up to here L and the rotation matrix live in LDS, above in the scratch
+constexpr int R360_TOPO_MAX_SWEEPS = 40;       // Jacobi sweeps at most (status 1 when they run out)
+constexpr int R360_TOPO_FIXED_DOUBLES = 1800;  // the workgroup's small LDS arrays (k_topo_level), in doubles
+constexpr size_t R360_TOPO_LDS_BYTES =
+    sizeof(double) * (R360_TOPO_FIXED_DOUBLES + 2 * (size_t)R360_TOPO_LDS_MAX_NODES * R360_TOPO_LDS_MAX_NODES);
+constexpr int R360_TOPO_CHUNK = 32;            // graphs of a batch that run together (1 MiB of scratch each)
+struct TopoCluster { int graph, off, n, level; };   // its index list: idx[graph][off .. off + n)
+struct TopoRecord { double cut; int graph, off, n, level, n1, split, sweeps, status, first, pad; };   // one per bisection; first: the cluster's lowest node
+// What one level's launch reads and writes.  Per graph g: its matrix A + a_off[g] (n_g x n_g fp32), the index lists
+// idx_in / idx_out [g][R360_TOPO_MAX_NODES], the labels (a final part's first node) and 2 x 256 x 256 doubles of scratch.
+struct TopoArgs {
+    const float* A = nullptr;
+    const long long* a_off = nullptr;
+    const int* gn = nullptr;
+    const TopoCluster* pending = nullptr;
+    TopoCluster* next = nullptr;
+    int* next_count = nullptr;
+    const int* idx_in = nullptr;
+    int* idx_out = nullptr;
+    int* label = nullptr;
+    TopoRecord* rec = nullptr;      // this level's records, one per pending cluster
+    double* scratch = nullptr;
+    double threshold = 0.8;
+    int min_cluster = 3, recursive = 1;
+    double* eig_out = nullptr;      // the bisect hook (cluster 0 of the launch): eigenvalues ascending, the Fiedler
+    double* fiedler_out = nullptr;  // vector and the sides (1 / 2), R360_TOPO_MAX_NODES each; NULL otherwise
+    int* side_out = nullptr;
+};
+struct TopoState {
+    int cap_graphs = 0;
+    size_t cap_A = 0;
+    float* A = nullptr;
+    long long* a_off = nullptr;
+    int* gn = nullptr;
+    TopoCluster* pending[2] = {nullptr, nullptr};
+    int* idx[2] = {nullptr, nullptr};
+    int* label = nullptr;
+    TopoRecord* rec = nullptr;
+    double* scratch = nullptr;
+    int* count = nullptr;
+    int* h_count = nullptr;         // pinned
+    double* hook_d = nullptr;       // [2][R360_TOPO_MAX_NODES]
+    int* hook_i = nullptr;          // [R360_TOPO_MAX_NODES]
+    bool lds_attr = false;
+};
+void topo_state_free(TopoState& S);
+int launch_topo_level(hipStream_t st, const TopoArgs& a, int n_pending);
+
 // ------------------------------------------------------------------ host objects
 struct r360_plane_queue;
 struct VoxSlot;
 struct r360_ctx {
     MapState vmap;                         // voxel-filter scratch and the context's global map (host/map.cpp)
     GicpState gicp;                        // Generalized-ICP clouds, indices and pass buffers (host/gicp.cpp)
+    TopoState topo;                        // spectral partitioning: matrices, cluster lists, scratch (host/topo.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
     hipStream_t stream = nullptr;
