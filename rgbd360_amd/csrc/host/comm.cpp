@@ -14,6 +14,7 @@
 #include <rccl/rccl.h>
 
 #include "../r360_internal.h"
+#include "devmem.h"
 
 // RCCL is loaded on first use (dlopen), so single-GPU users of the library never load it.
 namespace {
@@ -59,8 +60,7 @@ struct r360_comm {
     int device = 0, nranks = 1, rank = 0;
     ncclComm_t comm = nullptr;
     hipStream_t stream = nullptr;
-    void* d_buf = nullptr;   // staging: send slice + nranks receive slices
-    size_t cap = 0;
+    DevBuf<char> d_buf;      // staging: send slice + nranks receive slices
 };
 
 static_assert(sizeof(ncclUniqueId) == 128, "RCCL unique id size");
@@ -107,21 +107,13 @@ extern "C" void r360_comm_destroy(r360_comm* c) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     rccl().commDestroy(c->comm);
-    hipFree(c->d_buf);
+    c->d_buf.reset();
     hipStreamDestroy(c->stream);
     delete c;
 }
 
-static int comm_reserve(r360_comm* c, size_t bytes) {
-    if (c->cap >= bytes) return 0;
-    R360_HIP(hipStreamSynchronize(c->stream));
-    if (c->d_buf) R360_HIP(hipFree(c->d_buf));
-    c->d_buf = nullptr;
-    c->cap = 0;
-    R360_HIP(hipMalloc(&c->d_buf, bytes));
-    c->cap = bytes;
-    return 0;
-}
+// the staging buffer has no context: growing it waits for the communicator's own stream
+static int comm_reserve(r360_comm* c, size_t bytes) { return c->d_buf.reserve(nullptr, bytes, c->stream); }
 
 // recv = the nranks send buffers of `bytes` each, in rank order (ncclAllGather over xGMI)
 extern "C" int r360_comm_allgather(r360_comm* c, const void* send, void* recv, size_t bytes) {
@@ -129,7 +121,7 @@ extern "C" int r360_comm_allgather(r360_comm* c, const void* send, void* recv, s
     R360_HIP(hipSetDevice(c->device));
     const size_t slot = (bytes + 255) & ~size_t(255);
     if (int rc = comm_reserve(c, slot * (1 + (size_t)c->nranks))) return rc;
-    char* d_send = static_cast<char*>(c->d_buf);
+    char* d_send = c->d_buf.get();
     char* d_recv = d_send + slot;
     R360_HIP(hipMemcpyAsync(d_send, send, bytes, hipMemcpyHostToDevice, c->stream));
     // the receive slices are `bytes` apart (ncclAllGather's layout)
@@ -145,9 +137,10 @@ extern "C" int r360_comm_allreduce_max(r360_comm* c, double* v, int n) {
     R360_HIP(hipSetDevice(c->device));
     const size_t bytes = sizeof(double) * (size_t)n;
     if (int rc = comm_reserve(c, bytes)) return rc;
-    R360_HIP(hipMemcpyAsync(c->d_buf, v, bytes, hipMemcpyHostToDevice, c->stream));
-    R360_NCCL(rccl().allReduce(c->d_buf, c->d_buf, (size_t)n, ncclFloat64, ncclMax, c->comm, c->stream));
-    R360_HIP(hipMemcpyAsync(v, c->d_buf, bytes, hipMemcpyDeviceToHost, c->stream));
+    char* d_buf = c->d_buf.get();
+    R360_HIP(hipMemcpyAsync(d_buf, v, bytes, hipMemcpyHostToDevice, c->stream));
+    R360_NCCL(rccl().allReduce(d_buf, d_buf, (size_t)n, ncclFloat64, ncclMax, c->comm, c->stream));
+    R360_HIP(hipMemcpyAsync(v, d_buf, bytes, hipMemcpyDeviceToHost, c->stream));
     R360_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }

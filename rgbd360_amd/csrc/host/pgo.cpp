@@ -9,6 +9,7 @@
 #include <numeric>
 
 #include "../r360_internal.h"
+#include "devmem.h"
 
 struct r360_graph {
     r360_ctx* ctx = nullptr;
@@ -18,35 +19,26 @@ struct r360_graph {
     std::vector<int> ij;          // [m][2]
     std::vector<double> Z;        // [m][16] column-major
     std::vector<double> Om;       // [m][36] symmetrised
-    // device
+    // device: the handle owns the buffers (host/devmem.h); D is the view of them the kernels take, refilled by prepare
+    struct {
+        DevBuf<int2> ij;
+        DevBuf<int> vfree, fidx, vptr, ventry, vblk, rowptr, colidx, diag;
+        DevBuf<double> Z, Om, Hs, bs, lin, cost, vals, b, minv;
+    } own;
     PgoDev D;
-    size_t cap_n = 0, cap_m = 0, cap_nf = 0, cap_ent = 0, cap_nnzb = 0;
-    double* pose[2] = {nullptr, nullptr};   // [n][12] row-major 3x4: the current and the trial poses
-    double* delta = nullptr;                // [6 nf]
-    double* vec = nullptr;                  // multi-launch PCG: x, r, z, q, p0, p1
-    double* partials = nullptr;             // max(R360_PGO_MAXB, 3 * PCG workgroups)
-    size_t cap_part = 0;
-    PgoOut* d_out = nullptr;
-    PgoOut* h_out = nullptr;                // pinned
-    PgoCgState* d_cg = nullptr;
-    PgoCgState* h_cg = nullptr;             // pinned
+    DevBuf<double> pose[2];                 // [n][12] row-major 3x4: the current and the trial poses
+    DevBuf<double> delta;                   // [6 nf]
+    DevBuf<double> vec;                     // multi-launch PCG: x, r, z, q, p0, p1
+    DevBuf<double> partials;                // max(R360_PGO_MAXB, 3 * PCG workgroups)
+    DevBuf<PgoOut> d_out;
+    PinnedBuf<PgoOut> h_out;
+    DevBuf<PgoCgState> d_cg;
+    PinnedBuf<PgoCgState> h_cg;
 };
 
 namespace {
 
 constexpr int MAX_VERTICES = 1 << 20;
-
-template <class T>
-int grow(r360_ctx* ctx, T*& p, size_t have, size_t need) {
-    if (need <= have && p) return 0;
-    if (p) {
-        if (ctx_wait(ctx)) return -1;
-        R360_HIP(hipFree(p));
-        p = nullptr;
-    }
-    R360_HIP(hipMalloc(&p, sizeof(T) * std::max<size_t>(need, 1)));
-    return 0;
-}
 
 bool finite_n(const double* v, int n) {
     for (int k = 0; k < n; ++k)
@@ -152,40 +144,24 @@ int prepare(r360_graph* g) {
     if (bind_device(ctx->device)) return -1;
     const int nf = (int)S.vfree.size(), nnzb = (int)S.colidx.size();
     const size_t ent = S.ventry.size();
-    PgoDev& D = g->D;
-    if ((size_t)n > g->cap_n || !g->pose[0]) {
-        if (grow(ctx, g->pose[0], 0, 12 * (size_t)n) || grow(ctx, g->pose[1], 0, 12 * (size_t)n) || grow(ctx, D.fidx, 0, n)) return -1;
-        g->cap_n = n;
-    }
-    if ((size_t)m > g->cap_m || !D.ij) {
-        const size_t mm = std::max(m, 1);
-        if (grow(ctx, D.ij, 0, mm) || grow(ctx, D.Z, 0, 12 * mm) || grow(ctx, D.Om, 0, 36 * mm) ||
-            grow(ctx, D.Hs, 0, R360_PGO_SLOT_H * mm) || grow(ctx, D.bs, 0, R360_PGO_SLOT_B * mm) ||
-            grow(ctx, D.lin, 0, R360_PGO_SLOT_LIN * mm) || grow(ctx, D.cost, 0, mm))
-            return -1;
-        g->cap_m = m;
-    }
-    if ((size_t)nf > g->cap_nf || !D.vfree) {
-        const size_t f = std::max(nf, 1);
-        if (grow(ctx, D.vfree, 0, f) || grow(ctx, D.vptr, 0, f + 1) || grow(ctx, D.rowptr, 0, f + 1) || grow(ctx, D.diag, 0, f) ||
-            grow(ctx, D.b, 0, 6 * f) || grow(ctx, D.minv, 0, 36 * f) || grow(ctx, g->delta, 0, 6 * f) || grow(ctx, g->vec, 0, 36 * f))
-            return -1;
-        g->cap_nf = nf;
-    }
-    if (ent > g->cap_ent || !D.ventry) {
-        if (grow(ctx, D.ventry, 0, ent) || grow(ctx, D.vblk, 0, ent)) return -1;
-        g->cap_ent = ent;
-    }
-    if ((size_t)nnzb > g->cap_nnzb || !D.colidx) {
-        if (grow(ctx, D.colidx, 0, (size_t)nnzb) || grow(ctx, D.vals, 0, 36 * (size_t)std::max(nnzb, 1))) return -1;
-        g->cap_nnzb = nnzb;
-    }
+    auto& O = g->own;
+    const size_t mm = std::max(m, 1), f = std::max(nf, 1), e1 = std::max<size_t>(ent, 1), nz = std::max(nnzb, 1);
     const size_t npart = std::max<size_t>(R360_PGO_MAXB, 3 * (size_t)((6 * nf + R360_PGO_CGM_TPB - 1) / R360_PGO_CGM_TPB));
-    if (npart > g->cap_part) {
-        if (grow(ctx, g->partials, 0, npart)) return -1;
-        g->cap_part = npart;
-    }
+    if (g->pose[0].reserve(ctx, 12 * (size_t)n) || g->pose[1].reserve(ctx, 12 * (size_t)n) || O.fidx.reserve(ctx, n) ||
+        O.ij.reserve(ctx, mm) || O.Z.reserve(ctx, 12 * mm) || O.Om.reserve(ctx, 36 * mm) ||
+        O.Hs.reserve(ctx, R360_PGO_SLOT_H * mm) || O.bs.reserve(ctx, R360_PGO_SLOT_B * mm) ||
+        O.lin.reserve(ctx, R360_PGO_SLOT_LIN * mm) || O.cost.reserve(ctx, mm) ||
+        O.vfree.reserve(ctx, f) || O.vptr.reserve(ctx, f + 1) || O.rowptr.reserve(ctx, f + 1) || O.diag.reserve(ctx, f) ||
+        O.b.reserve(ctx, 6 * f) || O.minv.reserve(ctx, 36 * f) || g->delta.reserve(ctx, 6 * f) || g->vec.reserve(ctx, 36 * f) ||
+        O.ventry.reserve(ctx, e1) || O.vblk.reserve(ctx, e1) || O.colidx.reserve(ctx, nz) || O.vals.reserve(ctx, 36 * nz) ||
+        g->partials.reserve(ctx, npart))
+        return -1;
+    PgoDev& D = g->D;
     D.n = n; D.m = m; D.nf = nf; D.nnzb = nnzb;
+    D.ij = O.ij.get(); D.Z = O.Z.get(); D.Om = O.Om.get(); D.vfree = O.vfree.get(); D.fidx = O.fidx.get();
+    D.vptr = O.vptr.get(); D.ventry = O.ventry.get(); D.vblk = O.vblk.get(); D.rowptr = O.rowptr.get();
+    D.colidx = O.colidx.get(); D.diag = O.diag.get(); D.Hs = O.Hs.get(); D.bs = O.bs.get(); D.lin = O.lin.get();
+    D.cost = O.cost.get(); D.vals = O.vals.get(); D.b = O.b.get(); D.minv = O.minv.get();
     std::vector<double> P(12 * (size_t)n), Z(12 * (size_t)m);
     std::vector<int2> ij(m);
     for (int v = 0; v < n; ++v) pose12(&g->poses[16 * (size_t)v], &P[12 * (size_t)v]);
@@ -194,7 +170,7 @@ int prepare(r360_graph* g) {
         ij[e] = make_int2(g->ij[2 * e], g->ij[2 * e + 1]);
     }
     hipStream_t st = ctx->stream;
-    if (upload(st, g->pose[0], P) || upload(st, D.Z, Z) || upload(st, D.ij, ij) || upload(st, D.Om, g->Om) ||
+    if (upload(st, g->pose[0].get(), P) || upload(st, D.Z, Z) || upload(st, D.ij, ij) || upload(st, D.Om, g->Om) ||
         upload(st, D.fidx, S.fidx) || upload(st, D.vfree, S.vfree) || upload(st, D.vptr, S.vptr) ||
         upload(st, D.ventry, S.ventry) || upload(st, D.vblk, S.vblk) || upload(st, D.rowptr, S.rowptr) ||
         upload(st, D.colidx, S.colidx) || upload(st, D.diag, S.diag))
@@ -227,21 +203,22 @@ int solve(r360_graph* g, int form, double lambda, double tol, int maxit, double*
     r360_ctx* ctx = g->ctx;
     if (launch_pgo_precond(ctx->stream, g->D, lambda)) return -1;
     if (form == 1) {
-        *delta = g->delta;
-        return launch_pgo_cg1(ctx->stream, g->D, lambda, tol * tol, maxit, g->delta, g->d_out);
+        *delta = g->delta.get();
+        return launch_pgo_cg1(ctx->stream, g->D, lambda, tol * tol, maxit, g->delta.get(), g->d_out.get());
     }
-    *delta = g->vec;
-    return launch_pgo_cgm(ctx, g->D, lambda, tol * tol, maxit, g->vec, g->partials, g->d_cg, g->h_cg, g->d_out);
+    *delta = g->vec.get();
+    return launch_pgo_cgm(ctx, g->D, lambda, tol * tol, maxit, g->vec.get(), g->partials.get(), g->d_cg.get(), g->h_cg.get(),
+                          g->d_out.get());
 }
 
 int read_out(r360_graph* g) {
-    R360_HIP(hipMemcpyAsync(g->h_out, g->d_out, sizeof(PgoOut), hipMemcpyDeviceToHost, g->ctx->stream));
+    R360_HIP(hipMemcpyAsync(g->h_out.get(), g->d_out.get(), sizeof(PgoOut), hipMemcpyDeviceToHost, g->ctx->stream));
     return ctx_wait(g->ctx);
 }
 
 int linearise(r360_graph* g, const double* poses) {
-    if (launch_pgo_linearise(g->ctx->stream, g->D, poses, false, g->partials, &g->d_out->F)) return -1;
-    return launch_pgo_assemble(g->ctx->stream, g->D, g->d_out);
+    if (launch_pgo_linearise(g->ctx->stream, g->D, poses, false, g->partials.get(), &g->d_out.get()->F)) return -1;
+    return launch_pgo_assemble(g->ctx->stream, g->D, g->d_out.get());
 }
 
 }  // namespace
@@ -249,18 +226,13 @@ int linearise(r360_graph* g, const double* poses) {
 extern "C" int r360_graph_create(r360_ctx* ctx, r360_graph** out) {
     CHECK_ARG(ctx && out, "null arg");
     if (bind_device(ctx->device)) return -1;
-    r360_graph* g = new r360_graph;
+    std::unique_ptr<r360_graph> g(new r360_graph);
     g->ctx = ctx;
     g->device = ctx->device;
-    if (hipMalloc(&g->d_out, sizeof(PgoOut)) != hipSuccess || hipMalloc(&g->d_cg, sizeof(PgoCgState)) != hipSuccess ||
-        hipHostMalloc(&g->h_out, sizeof(PgoOut), hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(&g->h_cg, sizeof(PgoCgState), hipHostMallocDefault) != hipSuccess ||
-        hipMemsetAsync(g->d_out, 0, sizeof(PgoOut), ctx->stream) != hipSuccess) {
-        r360_set_error("graph: cannot allocate the read-back buffers");
-        r360_graph_destroy(g);
+    if (g->d_out.reserve_zeroed(ctx, 1, ctx->stream) || g->d_cg.reserve(ctx, 1) || g->h_out.reserve(ctx, 1) ||
+        g->h_cg.reserve(ctx, 1))
         return -1;
-    }
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -268,13 +240,6 @@ extern "C" void r360_graph_destroy(r360_graph* g) {
     if (!g) return;
     // hipFree waits for the device's work itself; the context is not touched, it may be gone already
     hipSetDevice(g->device);
-    PgoDev& D = g->D;
-    hipFree(D.ij); hipFree(D.Z); hipFree(D.Om); hipFree(D.vfree); hipFree(D.fidx); hipFree(D.vptr); hipFree(D.ventry);
-    hipFree(D.vblk); hipFree(D.rowptr); hipFree(D.colidx); hipFree(D.diag); hipFree(D.Hs); hipFree(D.bs); hipFree(D.lin);
-    hipFree(D.cost); hipFree(D.vals); hipFree(D.b); hipFree(D.minv);
-    hipFree(g->pose[0]); hipFree(g->pose[1]); hipFree(g->delta); hipFree(g->vec); hipFree(g->partials);
-    hipFree(g->d_out); hipFree(g->d_cg);
-    hipHostFree(g->h_out); hipHostFree(g->h_cg);
     delete g;
 }
 
@@ -367,14 +332,15 @@ extern "C" int r360_graph_optimize(r360_graph* g, const r360_graph_params* param
     if (int rc = prepare(g)) return rc;
     r360_ctx* ctx = g->ctx;
     const PgoDev& D = g->D;
+    const PgoOut& out = *g->h_out.get();   // pinned: what the last read_out brought back
     const int cg_max = p.cg_max_iterations > 0 ? p.cg_max_iterations : 12 * D.nf;
     int cur = 0;
-    if (linearise(g, g->pose[cur]) || read_out(g)) return -1;
-    double F = g->h_out->F;
+    if (linearise(g, g->pose[cur].get()) || read_out(g)) return -1;
+    double F = out.F;
     st.F_initial = st.F_final = F;
-    double lambda = 1e-5 * g->h_out->maxdiag, nu = 2.0;
+    double lambda = 1e-5 * out.maxdiag, nu = 2.0;
     st.lambda = lambda;
-    if (F == 0.0 || g->h_out->maxb == 0.0) {
+    if (F == 0.0 || out.maxb == 0.0) {
         if (stats) *stats = st;
         return 0;
     }
@@ -386,19 +352,21 @@ extern "C" int r360_graph_optimize(r360_graph* g, const r360_graph_params* param
         for (int trial = 0; trial < p.max_trials; ++trial) {
             double* delta = nullptr;
             if (int rc = solve(g, form, lambda, p.cg_tolerance, cg_max, &delta)) return rc;
-            if (launch_pgo_update(ctx->stream, D, g->pose[cur], delta, lambda, g->pose[1 - cur], g->d_out)) return -1;
-            if (launch_pgo_linearise(ctx->stream, D, g->pose[1 - cur], true, g->partials, &g->d_out->F)) return -1;
+            if (launch_pgo_update(ctx->stream, D, g->pose[cur].get(), delta, lambda, g->pose[1 - cur].get(), g->d_out.get()))
+                return -1;
+            if (launch_pgo_linearise(ctx->stream, D, g->pose[1 - cur].get(), true, g->partials.get(), &g->d_out.get()->F))
+                return -1;
             if (read_out(g)) return -1;
             ++st.trials;
-            st.cg_iterations += g->h_out->cg_iters;
-            st.cg_iterations_max = std::max(st.cg_iterations_max, g->h_out->cg_iters);
-            if (!g->h_out->cg_done) {
+            st.cg_iterations += out.cg_iters;
+            st.cg_iterations_max = std::max(st.cg_iterations_max, out.cg_iters);
+            if (!out.cg_done) {
                 st.status = R360_GRAPH_CG_NOT_CONVERGED;
                 stop = true;
                 break;
             }
-            F1 = g->h_out->F;
-            const double rho = (F - F1) / g->h_out->pred;
+            F1 = out.F;
+            const double rho = (F - F1) / out.pred;
             if (std::isfinite(F1) && rho > 0.0) {
                 const double c = 2.0 * rho - 1.0;
                 lambda *= std::max(1.0 / 3.0, 1.0 - c * c * c);
@@ -428,12 +396,12 @@ extern "C" int r360_graph_optimize(r360_graph* g, const r360_graph_params* param
             st.status = R360_GRAPH_ITERATION_LIMIT;
             break;
         }
-        if (linearise(g, g->pose[cur])) return -1;
+        if (linearise(g, g->pose[cur].get())) return -1;
     }
     if (st.iterations > 0) {   // the free vertices' new poses; the others keep their bytes
         std::vector<double> P(12 * (size_t)D.n);
         if (ctx_wait(ctx)) return -1;
-        R360_HIP(hipMemcpy(P.data(), g->pose[cur], sizeof(double) * P.size(), hipMemcpyDeviceToHost));
+        R360_HIP(hipMemcpy(P.data(), g->pose[cur].get(), sizeof(double) * P.size(), hipMemcpyDeviceToHost));
         for (int v = 0; v < D.n; ++v) {
             if (g->fixed[v]) continue;
             for (int r = 0; r < 3; ++r)
@@ -455,8 +423,8 @@ extern "C" int r360_graph_eval(r360_graph* g, double* F, double* b, double* H, i
     if ((b || H) && cap < N) { r360_set_error("graph: capacity %d < %d unknowns", cap, N); return -4; }
     if (int rc = prepare(g)) return rc;
     const PgoDev& D = g->D;
-    if (linearise(g, g->pose[0]) || read_out(g)) return -1;
-    if (F) *F = g->h_out->F;
+    if (linearise(g, g->pose[0].get()) || read_out(g)) return -1;
+    if (F) *F = g->h_out.get()->F;
     if (b && N) R360_HIP(hipMemcpy(b, D.b, sizeof(double) * N, hipMemcpyDeviceToHost));
     if (H && N) {
         std::vector<int> rowptr(D.nf + 1), colidx(D.nnzb);
@@ -493,16 +461,17 @@ extern "C" int r360_graph_solve(r360_graph* g, const r360_graph_params* params, 
     int form = 0;
     if (int rc = pick_form(&p, nfree, &form)) return rc;
     if (int rc = prepare(g)) return rc;
-    if (linearise(g, g->pose[0])) return -1;
+    if (linearise(g, g->pose[0].get())) return -1;
     double* d = nullptr;
     const int cg_max = p.cg_max_iterations > 0 ? p.cg_max_iterations : 12 * nfree;
     if (int rc = solve(g, form, lambda, p.cg_tolerance, cg_max, &d)) return rc;
     if (read_out(g)) return -1;
     R360_HIP(hipMemcpy(delta, d, sizeof(double) * N, hipMemcpyDeviceToHost));
-    if (iterations) *iterations = g->h_out->cg_iters;
-    if (rel_residual) *rel_residual = g->h_out->bb > 0.0 ? std::sqrt(g->h_out->rr / g->h_out->bb) : 0.0;
+    const PgoOut& out = *g->h_out.get();
+    if (iterations) *iterations = out.cg_iters;
+    if (rel_residual) *rel_residual = out.bb > 0.0 ? std::sqrt(out.rr / out.bb) : 0.0;
     if (form_out) *form_out = form;
-    return g->h_out->cg_done ? 0 : 1;
+    return out.cg_done ? 0 : 1;
 }
 
 extern "C" int r360_graph_save(const r360_graph* g, const char* path) {

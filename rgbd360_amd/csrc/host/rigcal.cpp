@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../r360_internal.h"
+#include "devmem.h"
 
 struct r360_rigcal {
     r360_ctx* ctx = nullptr;      // may be null: rows and files only
@@ -19,20 +20,19 @@ struct r360_rigcal {
     double init[8][16];           // column-major
     double est[8][16];
     double cov[8][9] = {};        // the collector's sums of n_i n_j^T per adjacent pair, (0, 7) under 7
-    // device
+    // device: the handle owns the buffers (host/devmem.h); D is the view of them the kernels take, refilled by upload
     bool dirty = true;
     RigcalDev D;
-    double* d_rows = nullptr;
-    int* d_tab = nullptr;         // pair_start [29], wg_start [29], wg_pair [nwg]
-    size_t cap_rows = 0, cap_tab = 0, cap_rec = 0;
-    double* d_rot = nullptr;      // [2][8][9]
-    double* h_out = nullptr;      // pinned [R360_RIGCAL_OUT]
+    DevBuf<double> d_rows;
+    DevBuf<int> d_tab;            // pair_start [29], wg_start [29], wg_pair [nwg]
+    DevBuf<double> d_rec;         // D.rec
+    DevBuf<double> d_out;         // D.out
+    DevBuf<double> d_rot;         // [2][8][9]
+    PinnedBuf<double> h_out;      // [R360_RIGCAL_OUT]
     int pair_start[R360_RIGCAL_PAIRS + 1] = {0};
     // trimmer
-    int* d_counts = nullptr;      // counts [cap_trials], flags [cap_trials]
-    size_t cap_trials = 0;
-    unsigned char* d_mask = nullptr;
-    size_t cap_mask = 0;
+    DevBuf<int> d_counts;         // counts [n], flags [n] of one chunk of n trials
+    DevBuf<unsigned char> d_mask;
 };
 
 namespace {
@@ -228,19 +228,7 @@ void vertical_alignment(double est[8][16]) {
     }
 }
 
-template <class T>
-int grow(r360_ctx* ctx, T*& p, size_t& have, size_t need) {
-    if (need <= have && p) return 0;
-    if (p) {
-        if (ctx_wait(ctx)) return -1;
-        R360_HIP(hipFree(p));
-        p = nullptr;
-        have = 0;
-    }
-    R360_HIP(hipMalloc(&p, sizeof(T) * std::max<size_t>(need, 1)));
-    have = std::max<size_t>(need, 1);
-    return 0;
-}
+size_t at_least_1(size_t need) { return std::max<size_t>(need, 1); }   // an empty set still has its buffers
 
 int need_gpu(const r360_rigcal* h) {
     CHECK_ARG(h, "null arg");
@@ -268,20 +256,21 @@ int upload(r360_rigcal* h) {
     tab[2 * R360_RIGCAL_PAIRS + 1] = nwg;
     memcpy(h->pair_start, tab.data(), sizeof h->pair_start);
     r360_ctx* ctx = h->ctx;
-    if (grow(ctx, h->d_rows, h->cap_rows, rows.size()) || grow(ctx, h->d_tab, h->cap_tab, tab.size()) ||
-        grow(ctx, h->D.rec, h->cap_rec, (size_t)R360_RIGCAL_REC * nwg))
+    if (h->d_rows.reserve(ctx, at_least_1(rows.size())) || h->d_tab.reserve(ctx, at_least_1(tab.size())) ||
+        h->d_rec.reserve(ctx, at_least_1((size_t)R360_RIGCAL_REC * nwg)))
         return -1;
     hipStream_t st = ctx->stream;
-    if (!rows.empty()) R360_HIP(hipMemcpyAsync(h->d_rows, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(h->d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, st));
+    if (!rows.empty()) R360_HIP(hipMemcpyAsync(h->d_rows.get(), rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(h->d_tab.get(), tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, st));
     if (ctx_wait(ctx)) return -1;   // the host vectors end here
     RigcalDev& D = h->D;
     D.n = n;
     D.nwg = nwg;
-    D.rows = h->d_rows;
-    D.pair_start = h->d_tab;
-    D.wg_start = h->d_tab + R360_RIGCAL_PAIRS + 1;
-    D.wg_pair = h->d_tab + 2 * (R360_RIGCAL_PAIRS + 1);
+    D.rows = h->d_rows.get();
+    D.pair_start = h->d_tab.get();
+    D.wg_start = h->d_tab.get() + R360_RIGCAL_PAIRS + 1;
+    D.wg_pair = h->d_tab.get() + 2 * (R360_RIGCAL_PAIRS + 1);
+    D.rec = h->d_rec.get();
     h->dirty = false;
     return 0;
 }
@@ -289,12 +278,13 @@ int upload(r360_rigcal* h) {
 // one linearisation at rot[0] (or the cost at rot[1]) into h->h_out
 int accumulate(r360_rigcal* h, const double rot[2][8][9], int mode, bool weighted, bool cost_only) {
     hipStream_t st = h->ctx->stream;
-    R360_HIP(hipMemcpyAsync(h->d_rot, rot, sizeof(double) * 144, hipMemcpyHostToDevice, st));
-    if (launch_rigcal_accum(st, h->D, h->d_rot, mode, weighted, cost_only)) return -1;
+    R360_HIP(hipMemcpyAsync(h->d_rot.get(), rot, sizeof(double) * 144, hipMemcpyHostToDevice, st));
+    if (launch_rigcal_accum(st, h->D, h->d_rot.get(), mode, weighted, cost_only)) return -1;
+    double* const h_out = h->h_out.get();
     if (cost_only)
-        R360_HIP(hipMemcpyAsync(h->h_out + R360_RIGCAL_OUT - 1, h->D.out + R360_RIGCAL_OUT - 1, sizeof(double), hipMemcpyDeviceToHost, st));
+        R360_HIP(hipMemcpyAsync(h_out + R360_RIGCAL_OUT - 1, h->D.out + R360_RIGCAL_OUT - 1, sizeof(double), hipMemcpyDeviceToHost, st));
     else
-        R360_HIP(hipMemcpyAsync(h->h_out, h->D.out, sizeof(double) * (R360_RIGCAL_OUT - 1), hipMemcpyDeviceToHost, st));
+        R360_HIP(hipMemcpyAsync(h_out, h->D.out, sizeof(double) * (R360_RIGCAL_OUT - 1), hipMemcpyDeviceToHost, st));
     return ctx_wait(h->ctx);
 }
 
@@ -351,34 +341,25 @@ extern "C" void r360_rigcal_specs(double rt8[8 * 16]) {
 
 extern "C" int r360_rigcal_create(r360_ctx* ctx, r360_rigcal** out) {
     CHECK_ARG(out, "null arg");
-    r360_rigcal* h = new r360_rigcal;
+    std::unique_ptr<r360_rigcal> h(new r360_rigcal);
     h->ctx = ctx;
     r360_rigcal_specs(&h->init[0][0]);
     memcpy(h->est, h->init, sizeof h->est);
     if (ctx) {
         h->device = ctx->device;
-        if (bind_device(ctx->device)) { delete h; return -1; }
-        if (hipMalloc(&h->d_rot, sizeof(double) * 144) != hipSuccess ||
-            hipMalloc(&h->D.out, sizeof(double) * R360_RIGCAL_OUT) != hipSuccess ||
-            hipHostMalloc(&h->h_out, sizeof(double) * R360_RIGCAL_OUT, hipHostMallocDefault) != hipSuccess) {
-            r360_set_error("rigcal: cannot allocate the read-back buffers");
-            r360_rigcal_destroy(h);
+        if (bind_device(ctx->device)) return -1;
+        if (h->d_rot.reserve(ctx, 144) || h->d_out.reserve(ctx, R360_RIGCAL_OUT) || h->h_out.reserve(ctx, R360_RIGCAL_OUT))
             return -1;
-        }
+        h->D.out = h->d_out.get();
     }
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
 extern "C" void r360_rigcal_destroy(r360_rigcal* h) {
     if (!h) return;
-    if (h->ctx) {
-        // hipFree waits for the device's work itself; the context is not touched, it may be gone already
-        hipSetDevice(h->device);
-        hipFree(h->d_rows); hipFree(h->d_tab); hipFree(h->D.rec); hipFree(h->D.out); hipFree(h->d_rot);
-        hipFree(h->d_counts); hipFree(h->d_mask);
-        hipHostFree(h->h_out);
-    }
+    // hipFree waits for the device's work itself; the context is not touched, it may be gone already
+    if (h->ctx) hipSetDevice(h->device);
     delete h;
 }
 
@@ -561,9 +542,9 @@ extern "C" int r360_rigcal_rotation(r360_rigcal* h, int weighted, r360_rigcal_st
         rots_of(h->est, rot[0]);
         memcpy(rot[1], rot[0], sizeof rot[0]);
         if (accumulate(h, rot, 0, weighted != 0, false)) return -1;
-        const double* H = h->h_out;
-        const double* g = h->h_out + 441;
-        const double* sc = h->h_out + 462;
+        const double* H = h->h_out.get();
+        const double* g = H + 441;
+        const double* sc = H + 462;
         st.iterations = it + 1;
         st.error[it] = sc[0];
         st.angle[it] = sc[1];
@@ -580,7 +561,7 @@ extern "C" int r360_rigcal_rotation(r360_rigcal* h, int weighted, r360_rigcal_st
         }
         const double e0 = sc[3];
         if (accumulate(h, rot, 0, weighted != 0, true)) return -1;
-        const double e1 = h->h_out[R360_RIGCAL_OUT - 1];
+        const double e1 = h->h_out.get()[R360_RIGCAL_OUT - 1];
         st.werr1[it] = e1;
         if (e1 < e0) {
             for (int k = 1; k < 8; ++k) set_rot(h->est[k], rot[1][k]);
@@ -613,11 +594,11 @@ extern "C" int r360_rigcal_translation(r360_rigcal* h, int weighted, r360_rigcal
     rots_of(h->est, rot[0]);
     memcpy(rot[1], rot[0], sizeof rot[0]);
     if (accumulate(h, rot, 1, weighted != 0, false)) return -1;
-    const double* H = h->h_out;
-    const double* g = h->h_out + 441;
+    const double* H = h->h_out.get();
+    const double* g = H + 441;
     st.rows = h->D.n;
     st.iterations = 1;
-    st.error[0] = h->h_out[462];
+    st.error[0] = H[462];
     st.conditioning[0] = conditioning21(H);
     double upd[21];
     if (!(st.conditioning[0] < THRESHOLD_CONDITIONING) || !solve21(H, g, upd)) {
@@ -648,9 +629,9 @@ extern "C" int r360_rigcal_eval(r360_rigcal* h, int mode, int weighted, double* 
     rots_of(h->est, rot[0]);
     memcpy(rot[1], rot[0], sizeof rot[0]);
     if (accumulate(h, rot, mode, weighted != 0, false)) return -1;
-    if (H) memcpy(H, h->h_out, sizeof(double) * 441);
-    if (g) memcpy(g, h->h_out + 441, sizeof(double) * 21);
-    if (scalars) memcpy(scalars, h->h_out + 462, sizeof(double) * 4);
+    if (H) memcpy(H, h->h_out.get(), sizeof(double) * 441);
+    if (g) memcpy(g, h->h_out.get() + 441, sizeof(double) * 21);
+    if (scalars) memcpy(scalars, h->h_out.get() + 462, sizeof(double) * 4);
     return 0;
 }
 
@@ -694,16 +675,13 @@ extern "C" int r360_rigcal_add_frame(r360_rigcal* h, r360_frame* f, const r360_r
     if (!keys.empty()) {
         r360_ctx* ctx = h->ctx;
         if (bind_device(ctx->device)) return -1;
-        int2* d_keys = nullptr;
-        longlong2* d_sums = nullptr;
-        R360_HIP(hipMalloc(&d_keys, sizeof(int2) * keys.size()));
-        if (hipMalloc(&d_sums, sizeof(longlong2) * keys.size()) != hipSuccess) { hipFree(d_keys); r360_set_error("rigcal: out of device memory"); return -1; }
-        int rc = hipMemcpyAsync(d_keys, keys.data(), sizeof(int2) * keys.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess;
-        if (!rc) rc = launch_rigcal_pixsum(ctx->stream, f->pl.labf, f->pl.w, f->pl.h, d_keys, (int)keys.size(), d_sums);
-        if (!rc) rc = hipMemcpyAsync(sums.data(), d_sums, sizeof(longlong2) * keys.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess;
+        DevBuf<int2> d_keys;
+        DevBuf<longlong2> d_sums;
+        if (d_keys.reserve(ctx, keys.size()) || d_sums.reserve(ctx, keys.size())) return -1;
+        int rc = hipMemcpyAsync(d_keys.get(), keys.data(), sizeof(int2) * keys.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess;
+        if (!rc) rc = launch_rigcal_pixsum(ctx->stream, f->pl.labf, f->pl.w, f->pl.h, d_keys.get(), (int)keys.size(), d_sums.get());
+        if (!rc) rc = hipMemcpyAsync(sums.data(), d_sums.get(), sizeof(longlong2) * keys.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess;
         if (!rc) rc = ctx_wait(ctx);
-        hipFree(d_keys);
-        hipFree(d_sums);
         if (rc) { r360_set_error("rigcal: the pixel sums failed"); return -1; }
     }
     struct Rig { double n[3], d, center; long long count; };
@@ -786,12 +764,13 @@ extern "C" int r360_rigcal_ransac_eval(r360_rigcal* h, int i, int j, const r360_
     if (n == 0) return 0;
     if (int rc = upload(h)) return rc;
     r360_ctx* ctx = h->ctx;
-    if (grow(ctx, h->d_counts, h->cap_trials, 2 * (size_t)n)) return -1;
+    if (h->d_counts.reserve(ctx, at_least_1(2 * (size_t)n))) return -1;
     const RigcalTrimParams kp = {p.dist, p.degenerate, p.max_redraws};
-    int* d_flags = h->d_counts + n;
-    if (launch_rigcal_ransac(ctx->stream, h->d_rows + (size_t)h->pair_start[pi] * 10, m, seed, trial0, n, kp, h->d_counts, d_flags)) return -1;
+    int* const d_counts = h->d_counts.get();
+    int* d_flags = d_counts + n;
+    if (launch_rigcal_ransac(ctx->stream, h->d_rows.get() + (size_t)h->pair_start[pi] * 10, m, seed, trial0, n, kp, d_counts, d_flags)) return -1;
     if (ctx_wait(ctx)) return -1;
-    R360_HIP(hipMemcpy(counts, h->d_counts, sizeof(int) * n, hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(counts, d_counts, sizeof(int) * n, hipMemcpyDeviceToHost));
     R360_HIP(hipMemcpy(flags, d_flags, sizeof(int) * n, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -839,12 +818,12 @@ extern "C" int r360_rigcal_trim(r360_rigcal* h, int i, int j, const r360_rigcal_
     }
     st.inliers = best;
     r360_ctx* ctx = h->ctx;
-    if (grow(ctx, h->d_mask, h->cap_mask, (size_t)m)) return -1;
+    if (h->d_mask.reserve(ctx, at_least_1((size_t)m))) return -1;
     const RigcalTrimParams kp = {p.dist, p.degenerate, p.max_redraws};
-    if (launch_rigcal_mask(ctx->stream, h->d_rows + (size_t)h->pair_start[pi] * 10, m, seed, st.winner, kp, h->d_mask)) return -1;
+    if (launch_rigcal_mask(ctx->stream, h->d_rows.get() + (size_t)h->pair_start[pi] * 10, m, seed, st.winner, kp, h->d_mask.get())) return -1;
     if (ctx_wait(ctx)) return -1;
     std::vector<unsigned char> hm(m);
-    R360_HIP(hipMemcpy(hm.data(), h->d_mask, m, hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(hm.data(), h->d_mask.get(), m, hipMemcpyDeviceToHost));
     std::vector<double> kept;
     kept.reserve((size_t)best * 10);
     for (int r = 0; r < m; ++r)
