@@ -1123,7 +1123,7 @@ extern "C" int r360_align360_async(r360_ctx* ctx, r360_frame* trg, r360_frame* s
     static const bool persist_env = R360_KNOB("R360_PERSIST", 0) != 0;
     // R360_PERSIST_MIN_LEVEL (experiment builds): only levels >= it run persistent, the finer ones pass by pass
     static const int persist_min = R360_KNOB("R360_PERSIST_MIN_LEVEL", 0);
-    bool persist = (ctx->persist_levels || persist_env) && !occlusion && !ctx->timing && !R360_POLL;
+    bool persist = (ctx->persist_levels || persist_env) && !occlusion && !ctx->timing;
     for (int l = persist_min; persist && l < p->n_pyr; ++l) persist = icp_level_persist_ok(ctx, src, l, method);
     if (persist) persist = persist_take(ctx);
     auto passes_of = [&]() -> int {
@@ -1144,7 +1144,7 @@ extern "C" int r360_align360_async(r360_ctx* ctx, r360_frame* trg, r360_frame* s
     // events; R360_NO_GRAPH=1 launches one by one (A/B)
     static const bool no_graph = R360_KNOB("R360_NO_GRAPH", 0) != 0;
     int rc;
-    if (no_graph || R360_POLL || occlusion || ctx->timing) rc = passes_of();
+    if (no_graph || occlusion || ctx->timing) rc = passes_of();
     else rc = align_graph_launch(ctx, trg, src, method, p, persist, passes_of);
     if (rc) {
         persist_release(ctx);
@@ -1281,10 +1281,6 @@ int align360_batch_enqueue(r360_ctx* ctx, int n, r360_frame* const* trg, r360_fr
         const int np = src[0]->lv[l].rows * src[0]->lv[l].cols;
         const IcpConst C = make_const(p, l, np, 0);
         const int passes = 1 + ((l == 0 && p->fixed_iters_level0 > 0) ? p->fixed_iters_level0 : p->max_iters);
-        // the coarse levels as one persistent launch each (k_icp_levels_batch); level 0 pass by pass
-        const int prc = launch_icp_levels_batch(ctx, jobs, n, src[0], l, method, C, passes);
-        if (prc < 0) return prc;
-        if (prc == 0) continue;
         for (int k = 0; k < passes; ++k)
             if (int rc = launch_icp_jobs(ctx, jobs, n, src[0], l, method, C, k == 0, 0)) return rc;
     }
@@ -1303,8 +1299,9 @@ extern "C" int r360_align360_batch_result(r360_ctx* ctx, float* pose_out, float*
     bool fault = false;
     for (int j = 0; j < n; ++j) fault = fault || ctx->h_bstate[j].fault;
     if (fault) {
-        // a persistent coarse-level launch timed out on a job's hand-off: its drained grid left group arrival counters
-        // part-way (only a pass's step workgroup resets them); zero every job's for the next batch on this ctx
+        // Guard: no batched launch is persistent, so no kernel of a batch sets the fault word (the batch's states start
+        // zeroed).  Should one read back set all the same, the job's group arrival counters may stand part-way (only a
+        // pass's step workgroup resets them): zero every job's for the next batch on this ctx
         R360_HIP(hipMemsetAsync(ctx->d_bgticket, 0, sizeof(unsigned) * R360_TICKET_STRIDE * R360_TICKET_GROUPS * n,
                                 ctx->stream));
         R360_HIP(hipStreamSynchronize(ctx->stream));

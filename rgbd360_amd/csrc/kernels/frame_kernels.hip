@@ -663,24 +663,13 @@ int launch_undistort(r360_frame* f) {
     return 0;
 }
 
-// experiment builds: R360_STITCH=4 forces the row-major k_stitch4
-static int stitch_form() {
-    static const int form = R360_KNOB("R360_STITCH", 0);
-    return form;
-}
-
 // A frame that only enters batched alignments (compact_all unset: the sequence runner's queued ring, or
 // r360_frame_set_compaction(f, 0)) is lean when its level 0 is streamed as the packed image (the condition under which
 // launch_pyramid skips level 0's compaction) and its stitch is the tiled one: the batched level-0 pass (PF 6), level
 // 1 and the level-0 gradients read pk only, so its build leaves d_sph_bgr, d_sph_depth and lv[0].p0 unwritten
 // (13 of the stitch's 17 bytes per pixel) until a reader asks for them (frame_level0_materialise).
-// R360_LEAN=0 (experiment builds) builds every frame in full.
 bool frame_level0_lean(const r360_frame* f) {
-    static const int pf_env = R360_KNOB("R360_ICP_PF", -1);
-    static const bool pyr_f2 = R360_KNOB("R360_PYR_F2", 0) != 0;   // level 1 from lv[0].p0
-    static const bool lean_on = R360_KNOB("R360_LEAN", 1) != 0;
-    return lean_on && !f->compact_all && !(pf_env == 4 || pf_env == 5) && !pyr_f2 && f->rows > 0 && f->lv[0].pk &&
-           f->lv[0].cols % 64 == 0 && stitch_form() != 4;
+    return !f->compact_all && f->rows > 0 && f->lv[0].pk && f->lv[0].cols % 64 == 0;
 }
 
 int launch_stitch(r360_frame* f, bool lean) {
@@ -688,12 +677,11 @@ int launch_stitch(r360_frame* f, bool lean) {
     const long n = (long)f->sph_rows * f->sph_cols;
     if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipStreamWaitEvent(f->ctx->stream, e, 0));   // a split upload's BGR copy
     const int slot = timing_begin(f->ctx, "k_stitch");
-    const int form = stitch_form();
-    if (lean && !(f->sph_cols % STT_C == 0 && form != 4)) {
+    if (lean && f->sph_cols % STT_C != 0) {
         r360_set_error("lean stitch: the tiled form only");
         return -1;
     }
-    if (f->sph_cols % STT_C == 0 && form != 4) {
+    if (f->sph_cols % STT_C == 0) {
         const dim3 grid((f->sph_cols / STT_C) * ((f->sph_rows + STT_R - 1) / STT_R));
         if (lean)
             hipLaunchKernelGGL(k_stitch_t<true>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
@@ -842,7 +830,6 @@ int launch_pyramid(r360_frame* f) {
         r360_set_error("sphere of %d x %d pixels is too large", f->lv[0].rows, f->lv[0].cols);
         return -1;
     }
-    static const bool pyr_f2 = R360_KNOB("R360_PYR_F2", 0) != 0;   // experiment builds: level 0 read as float2
     // launch 1: level 0's gradients, level 1 and its gradients, from level 0's packed image (half the bytes of its
     // float2 image, the same values) where the frame has one
     {
@@ -851,7 +838,7 @@ int launch_pyramid(r360_frame* f) {
         float2* p1 = more ? f->lv[1].p0 : nullptr;
         float4* tg1 = more ? f->lv[1].tg : nullptr;
         const dim3 grid(((L0.rows + L0_TR - 1) / L0_TR) * ((L0.cols + L0_TC - 1) / L0_TC));
-        if (L0.pk && !pyr_f2)
+        if (L0.pk)
             hipLaunchKernelGGL(k_prep_l0<LvPk>, grid, dim3(256), 0, f->ctx->stream, LvPk{L0.pk}, L0.rows, L0.cols, L0.tg,
                                p1, tg1, min_d, max_d);
         else
@@ -870,14 +857,11 @@ int launch_pyramid(r360_frame* f) {
     // the compacted points feed a lone alignment's passes (PF 5); batched passes stream the images (PF 6 at level 0
     // where its rows split into whole waves, PF 8 on levels of >= 64 columns), so frames that only enter batches
     // (f->compact_all unset: the sequence runner's queued ring) skip the levels a batched pass streams (built on
-    // request: r360_frame_get_points, or a form forced by R360_ICP_PF)
-    static const int pf_env = R360_KNOB("R360_ICP_PF", -1);
-    const bool skip_ok = !f->compact_all && !(pf_env == 4 || pf_env == 5);
+    // request: r360_frame_get_points)
     unsigned need = 0;
     for (int l = 0; l < f->n_levels; ++l) {
-        static const bool coarse_pf5 = R360_KNOB("R360_COARSE_PF5", 0) != 0;   // experiment builds (icp_kernels.hip)
-        const bool streamed = l == 0 && f->lv[0].pk ? f->lv[0].cols % 64 == 0 : f->lv[l].cols >= 64 && !coarse_pf5;
-        if (!skip_ok || !streamed) need |= 1u << l;
+        const bool streamed = l == 0 && f->lv[0].pk ? f->lv[0].cols % 64 == 0 : f->lv[l].cols >= 64;
+        if (f->compact_all || !streamed) need |= 1u << l;
     }
     f->compacted = need;
     return launch_src_compaction(f, need);

@@ -20,25 +20,17 @@
 
 namespace {
 
-#ifndef R360_ICP_TPB
-#define R360_ICP_TPB 256
-#endif
-#ifndef R360_PK_ACC
-#define R360_PK_ACC 0   // PF 6 sums J J^T with packed FMAs (contribute_pk)
-#endif
-#ifndef R360_ICP_MINB
-#define R360_ICP_MINB 5   // waves per SIMD (HIP launch_bounds 2nd arg): caps the pass at 102 VGPRs (94 used)
-#endif
 // 4 waves per workgroup, 5 workgroups per CU: 5 waves per SIMD (a 512-thread workgroup holds 2 waves per
 // SIMD, so 94 VGPRs still gave 4); with 512 workgroups per pass each wave streams twice the chunks, and a
 // batched launch (16 pairs) keeps every SIMD at 5 waves (17.8 vs 20.4 us per pair-pass, profiles/r2_v2)
-constexpr int TPB = R360_ICP_TPB;
+constexpr int TPB = 256;
+constexpr int ICP_MINB = 5;   // waves per SIMD (HIP launch_bounds 2nd arg): caps the pass at 102 VGPRs (94 used)
 constexpr int NW = TPB / 64;
 constexpr int RG = TPB / 16;  // record-reduction groups (16 lanes x 16 B per record)
 // the two-level record sum maps ticket group g to the final-stage row g (threadIdx.x >> 4) and sums rows k < RG
-static_assert(!R360_GROUP_SUM || R360_TICKET_GROUPS == RG, "R360_GROUP_SUM needs R360_TICKET_GROUPS == TPB / 16");
+static_assert(R360_TICKET_GROUPS == RG, "the group record sum needs R360_TICKET_GROUPS == TPB / 16");
 // gn_step_block (icp_gn.inc) runs the rank test on wave 1 and the solve on wave 2 of the step's workgroup
-static_assert(NW >= 3, "the GN step needs at least 3 waves per workgroup (R360_ICP_TPB >= 192)");
+static_assert(NW >= 3, "the GN step needs at least 3 waves per workgroup (TPB >= 192)");
 
 struct Pose12 { float R[9]; float t[3]; };
 
@@ -48,10 +40,6 @@ struct Pose12 { float R[9]; float t[3]; };
 // which had moved every gather next to its use and exposed its full latency once per pixel.
 struct Gather {
     __amdgpu_buffer_rsrc_t tg, trg;
-#ifdef R360_EXP_NOGATHER   // experiment builds only (tools/exp_variants.sh): no target loads
-    __device__ __forceinline__ float4 g(int t) const { const float v = (float)(t & 1023) * 1e-3f; return make_float4(v, -v, v, 0.5f * v); }
-    __device__ __forceinline__ float2 T(int t) const { return make_float2((float)(t & 255) * 4e-3f, 2.f); }
-#else
     __device__ __forceinline__ float4 g(int t) const {
         const auto v = __builtin_amdgcn_raw_buffer_load_b128(tg, t * 16, 0, 0);
         return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
@@ -60,7 +48,6 @@ struct Gather {
         const auto v = __builtin_amdgcn_raw_buffer_load_b64(trg, t * 8, 0, 0);
         return make_float2(__uint_as_float(v[0]), __uint_as_float(v[1]));
     }
-#endif
 };
 
 #ifdef R360_STAMPS
@@ -112,7 +99,6 @@ __device__ __forceinline__ void set_pixel(Proj& o, float rr, float cc, bool vali
 // boundary (or whose fast path produced NaN, at the poles) are flagged in o.fix and re-projected
 // exactly by project_fix before their target pixel is used.  Keeping this part branch-free lets the
 // scheduler interleave it with the accumulation of the previous chunk.
-template <bool FASTD = false>
 __device__ __forceinline__ Proj project(const Pose12& P, float d, float gray_s, float sp, float cp, float st, float ct,
                                         int nRows, int nCols, float half_nRows, float angle_res_inv, const IcpConst& C) {
     Proj o;
@@ -125,7 +111,7 @@ __device__ __forceinline__ Proj project(const Pose12& P, float d, float gray_s, 
     float Z = P.R[6] * lx + P.R[7] * ly + P.R[8] * lz; Z = Z + P.t[2];
     const float d2 = X * X + Y * Y + Z * Z;
     // |p'| is exact (it enters the depth residual); the projection itself uses hardware rsq/rcp
-    const float dist = FASTD ? __builtin_amdgcn_sqrtf(d2) : sqrtf(d2);
+    const float dist = sqrtf(d2);
     const float dist_inv = __builtin_amdgcn_rsqf(d2);
     const float phi_trg = r360m::asinf_fast(X * dist_inv);
     const float theta_trg = (float)((double)r360m::atan2f_fast(Y, Z) + R360_PI);
@@ -235,23 +221,12 @@ __device__ __forceinline__ float huber_rn(float e, float reg) {    // weightHube
     return a < reg ? 1.f : w;
 }
 
-__device__ __forceinline__ float huber_fast(float e, float reg) {   // weightHuber with hardware sqrt / rcp
-    const float a = fabsf(e);
-    const float w = __builtin_amdgcn_sqrtf(2 * reg * a - reg * reg) * __builtin_amdgcn_rcpf(a);
-    return a < reg ? 1.f : w;
-}
-
 // Residuals, weights and Jacobian rows of one projected pixel, accumulated branch-free: a pixel that
 // the reference skips contributes through selects that zero its row (never a multiply by 0, which
 // would let a NaN of an invalid pixel through).
-template <int METHOD, int OCC, bool FAST = false>
+template <int METHOD, int OCC>
 __device__ __forceinline__ void contribute(Acc& A, const Proj& o, const float4 G, const float2 T, int fl,
                                            float angle_res_inv, const IcpConst& C) {
-#ifdef R360_EXP_NOACC   // experiment builds only: keep the operands alive, skip the math
-    A.h[0] += o.vis ? G.x + G.y + G.z + G.w + T.x + T.y + o.X + o.dist : 0.f;
-    A.h[28] += o.vis ? 1.f : 0.f;
-    return;
-#endif
     constexpr bool photo = (METHOD == R360_PHOTO_CONSISTENCY || METHOD == R360_PHOTO_DEPTH);
     constexpr bool depth = (METHOD == R360_DEPTH_CONSISTENCY || METHOD == R360_PHOTO_DEPTH);
     const float X = o.X, Y = o.Y, Z = o.Z, dist = o.dist, dist_inv = o.dist_inv;
@@ -262,16 +237,12 @@ __device__ __forceinline__ void contribute(Acc& A, const Proj& o, const float4 G
     const bool p_ok = photo && o.vis && sal_p;
     const bool d_ok = depth && o.vis && (!photo || sal_p) && fin_d && sal_d;   // (:3064-3073)
     // exact error terms (they steer the accept/reject test :4715)
-    // FAST: hardware sqrt / rcp and float products (~1-2 ulp per term; the error and H / g sums keep
-    // their fp64 / summation-order tolerances)
     const float photoDiff = T.x - o.gray_s;
-    const float whp = FAST ? huber_fast(photoDiff, C.sd_photo) : huberf(photoDiff, C.sd_photo);
-    const float wEd = FAST ? whp * C.sd_photo_inv_f * photoDiff
-                           : (float)((double)whp * C.sd_photo_inv_d * photoDiff);         // (:2699-2700)
+    const float whp = huberf(photoDiff, C.sd_photo);
+    const float wEd = (float)((double)whp * C.sd_photo_inv_d * photoDiff);                 // (:2699-2700)
     const float depthDiff = T.y - dist;
     const float sd = C.sd_depth * T.y;
-    const float wd = FAST ? huber_fast(depthDiff, sd) * __builtin_amdgcn_rcpf(sd)
-                          : huberf(depthDiff, sd) / sd;                                   // (:3077-3078)
+    const float wd = huberf(depthDiff, sd) / sd;                                           // (:3077-3078)
     const float wEdep = wd * depthDiff;   // == (float)((double)wd * depthDiff): the f32 product is exact in f64
     // which terms enter the error and which Jacobian rows enter H / g
     bool jp = p_ok, jd = d_ok;
@@ -360,11 +331,6 @@ __device__ __forceinline__ int wave_count(bool b) { return __builtin_popcountll(
 template <int METHOD, int OCC>
 __device__ __forceinline__ void contribute_fast(Acc& A, WaveCnt& W, const Proj& o, const float4 G, const float2 T,
                                                 int fl, float angle_res_inv, const IcpConst& C) {
-#ifdef R360_EXP_NOACC   // experiment builds only: keep the operands alive, skip the math
-    A.h[0] += o.vis ? G.x + G.y + G.z + G.w + T.x + T.y + o.X + o.dist : 0.f;
-    W.c28 += wave_count(o.vis);
-    return;
-#endif
     constexpr bool photo = (METHOD == R360_PHOTO_CONSISTENCY || METHOD == R360_PHOTO_DEPTH);
     constexpr bool depth = (METHOD == R360_DEPTH_CONSISTENCY || METHOD == R360_PHOTO_DEPTH);
     const bool sal_p = !(fabsf(G.x) < C.thr_int && fabsf(G.y) < C.thr_int);
@@ -532,131 +498,6 @@ __device__ __forceinline__ void contribute_lean(Acc& A, WaveCnt& W, float& errf,
     }
 }
 
-#if R360_PK_ACC
-// Packed accumulation (PF 6): the 27 sums of J J^T and J r over a lane's pixels as 12 register pairs and 3 scalars,
-// updated by v_pk_fma_f32 (two FMAs per VALU instruction) instead of 27 v_fma per Jacobian row.  The row's
-// components are taken in the order q = (u1, u2 | u0, J3 | J4, J5 | r) and summed two rows of H at a time: pair
-// (q0, q1) times every q_j, j >= 1, and so on; the broadcast operand of each update comes from a half of an
-// existing pair (op_sel), so the update needs no register moves.  pk_fold maps the sums back to Acc's slots.
-typedef float f2v __attribute__((ext_vector_type(2)));
-struct AccPk {
-    f2v a0, a2, a3, a4, a5, a6;   // (q0 q0, q1 q1), (q0, q1) x q2 .. q6
-    f2v b0, b4, b5, b6;           // (q2 q2, q3 q3), (q2, q3) x q4 .. q6
-    f2v c0, c6;                   // (q4 q4, q5 q5), (q4, q5) x q6
-    float sa, sb, sc;             // q0 q1, q2 q3, q4 q5
-};
-__device__ __forceinline__ f2v pkfma(f2v a, f2v b, f2v c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f2v bc2(float x) { return f2v{x, x}; }
-
-__device__ __forceinline__ void pk_zero(AccPk& K) {
-    K.a0 = K.a2 = K.a3 = K.a4 = K.a5 = K.a6 = K.b0 = K.b4 = K.b5 = K.b6 = K.c0 = K.c6 = f2v{0.f, 0.f};
-    K.sa = K.sb = K.sc = 0.f;
-}
-
-// one Jacobian row J = [u0, u1, u2, p' x u] (u12 = (u1, u2)) with residual r
-__device__ __forceinline__ void pk_row(AccPk& K, f2v u12, float u0, float X, float Y, float Z, float r) {
-#pragma clang fp contract(fast)
-    const float J3 = Y * u12.y - Z * u12.x, J4 = Z * u0 - X * u12.y, J5 = X * u12.x - Y * u0;
-    const f2v Pb = f2v{u0, J3}, Pc = f2v{J4, J5};
-    K.a0 = pkfma(u12, u12, K.a0);
-    K.sa = __builtin_fmaf(u12.x, u12.y, K.sa);
-    K.a2 = pkfma(u12, bc2(u0), K.a2);
-    K.a3 = pkfma(u12, bc2(J3), K.a3);
-    K.a4 = pkfma(u12, bc2(J4), K.a4);
-    K.a5 = pkfma(u12, bc2(J5), K.a5);
-    K.a6 = pkfma(u12, bc2(r), K.a6);
-    K.b0 = pkfma(Pb, Pb, K.b0);
-    K.sb = __builtin_fmaf(u0, J3, K.sb);
-    K.b4 = pkfma(Pb, bc2(J4), K.b4);
-    K.b5 = pkfma(Pb, bc2(J5), K.b5);
-    K.b6 = pkfma(Pb, bc2(r), K.b6);
-    K.c0 = pkfma(Pc, Pc, K.c0);
-    K.sc = __builtin_fmaf(J4, J5, K.sc);
-    K.c6 = pkfma(Pc, bc2(r), K.c6);
-}
-
-// the packed sums into Acc's slots (0..20 upper-triangle H row-major, 21..26 g)
-__device__ __forceinline__ void pk_fold(Acc& A, const AccPk& K) {
-    A.h[6] += K.a0.x;  A.h[11] += K.a0.y; A.h[7] += K.sa;
-    A.h[1] += K.a2.x;  A.h[2] += K.a2.y;
-    A.h[8] += K.a3.x;  A.h[12] += K.a3.y;
-    A.h[9] += K.a4.x;  A.h[13] += K.a4.y;
-    A.h[10] += K.a5.x; A.h[14] += K.a5.y;
-    A.h[22] += K.a6.x; A.h[23] += K.a6.y;
-    A.h[0] += K.b0.x;  A.h[15] += K.b0.y; A.h[3] += K.sb;
-    A.h[4] += K.b4.x;  A.h[16] += K.b4.y;
-    A.h[5] += K.b5.x;  A.h[17] += K.b5.y;
-    A.h[21] += K.b6.x; A.h[24] += K.b6.y;
-    A.h[18] += K.c0.x; A.h[20] += K.c0.y; A.h[19] += K.sc;
-    A.h[25] += K.c6.x; A.h[26] += K.c6.y;
-}
-
-// contribute_lean<METHOD, false> (PF 6: the target depth is finite) with the Jacobian rows built in pairs and summed
-// by pk_row: u = J_proj^T [gx gy]^T as (A, B) = w (gx, gy) * (s, t), u0 = -B r2, (u1, u2) = A (Z, -Y) + B X (Y, Z)
-template <int METHOD>
-__device__ __forceinline__ void contribute_pk(AccPk& K, WaveCnt& W, float& errf, const Proj& o, const float4 G,
-                                              const float2 T, float angle_res_inv, const IcpConst& C) {
-    constexpr bool photo = (METHOD == R360_PHOTO_CONSISTENCY || METHOD == R360_PHOTO_DEPTH);
-    constexpr bool depth = (METHOD == R360_DEPTH_CONSISTENCY || METHOD == R360_PHOTO_DEPTH);
-    const bool sal_p = !(fabsf(G.x) < C.thr_int && fabsf(G.y) < C.thr_int);
-    const bool sal_d = !(fabsf(G.z) < C.thr_depth && fabsf(G.w) < C.thr_depth);
-    const bool p_ok = photo && o.vis && sal_p;
-    const bool d_ok = depth && o.vis && (!photo || sal_p) && sal_d;   // (:3064-3073)
-    float wp = 0.f, rp = 0.f, wd = 0.f, rd = 0.f;
-    {
-#pragma clang fp contract(fast)
-        if (photo) {
-            const float e = T.x - o.gray_s;
-            const float a = fabsf(e), k = C.sd_photo;
-            const float t = 2.f * k * a - k * k;
-            const float h = a < k ? 1.f : t * __builtin_amdgcn_rsqf(t * a * a);   // weightHuber (:545-554)
-            wp = p_ok ? h * C.sd_photo_inv_f : 0.f;                                 // (:3047)
-            rp = wp * e;
-        }
-        if (depth) {
-            const float e = T.y - o.dist;
-            const float a = fabsf(e), k = C.sd_depth * T.y, k2 = k * k;
-            const float t = 2.f * k * a - k2;
-            const bool in = a < k;
-            const float w = (in ? 1.f : t) * __builtin_amdgcn_rsqf(in ? k2 : t * a * a * k2);   // (:3077-3078)
-            wd = d_ok ? w : 0.f;
-            rd = d_ok ? w * e : 0.f;
-        }
-        errf += rp * rp + rd * rd;
-    }
-    W.c28 += wave_count(o.vis);                                                            // numVisiblePixels
-    W.c27 += (photo ? wave_count(p_ok) : 0) + (depth ? wave_count(d_ok) : 0);
-    const float X = o.X, Y = o.Y, Z = o.Z;
-    const float dist_inv = o.vis ? o.dist_inv : 0.5f;
-    {
-#pragma clang fp contract(fast)
-        const float r2 = o.vis ? Y * Y + Z * Z : 1.f;
-        // 1 / angle_res enters through the row's weight (no loop-invariant register pair)
-        const f2v st = f2v{__builtin_amdgcn_rcpf(r2), __builtin_amdgcn_rsqf(r2) * (dist_inv * dist_inv)};
-        const f2v YZ = f2v{Y, Z}, ZnY = f2v{Z, -Y};
-        auto row = [&](f2v g, float w, f2v& u12, float& u0) {
-            const f2v AB = (g * st) * bc2(w * angle_res_inv);
-            const float BX = AB.y * X;
-            u0 = -AB.y * r2;
-            u12 = pkfma(bc2(BX), YZ, bc2(AB.x) * ZnY);
-        };
-        if (photo) {
-            f2v u12;
-            float u0;
-            row(f2v{G.x, G.y}, wp, u12, u0);
-            pk_row(K, u12, u0, X, Y, Z, rp);
-        }
-        if (depth) {
-            f2v u12;
-            float u0;
-            row(f2v{G.z, G.w}, wd, u12, u0);
-            const float wdi = wd * dist_inv;
-            pk_row(K, pkfma(bc2(-wdi), YZ, u12), u0 - wdi * X, X, Y, Z, rd);
-        }
-    }
-}
-#endif
-
 // ---------------------------------------------------------------- GN step (thread 0 of last block)
 #include "icp_gn.inc"
 
@@ -717,10 +558,8 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
     __shared__ float s_red[NW][32];
     __shared__ double s_err[NW], s_errd[NW];
     __shared__ double s_fin[RG][32];
-#if !R360_POLL
     __shared__ int s_last;
-#endif
-    __shared__ int s_qn[NW];   // PF 5: deferred entries per wave
+    __shared__ int s_qn[NW];   // PF 5 / 6 / 8 / 9: deferred entries per wave
     __shared__ GnShared s_gn;
     __shared__ IcpState s_state;
 
@@ -792,11 +631,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
     WaveCnt W;   // PF 3: wave-uniform counts
     float errf = 0.f;   // PF 5: the lane's squared residuals in float
 
-    const int units = (nRows * nCols) >> 2;  // 4 pixels of one row per unit (nCols % 4 == 0)
-    const float4* src4 = reinterpret_cast<const float4*>(src);
-    const float4* st4 = reinterpret_cast<const float4*>(sinth);
-    const float4* ct4 = reinterpret_cast<const float4*>(costh);
-    const int cq = nCols >> 2;
     auto one = [&](float d, float g, float sp, float cp, float st, float ct, int fl) {
         Proj o = project(P, d, g, sp, cp, st, ct, nRows, nCols, half_nRows, angle_res_inv, C);
         project_fix(o, nRows, nCols, half_nRows, angle_res_inv);
@@ -804,89 +638,14 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         const float2 T = trg[o.t];
         contribute<METHOD, OCC>(A, o, G, T, fl, angle_res_inv, C);
     };
-    auto two = [&](float d0, float g0, float d1, float g1, float sp, float cp, float st0, float ct0, float st1,
-                   float ct1, int fl0, int fl1) {
-        // project both, issue both gathers, then the math (ILP + loads in flight)
-        Proj o0 = project(P, d0, g0, sp, cp, st0, ct0, nRows, nCols, half_nRows, angle_res_inv, C);
-        Proj o1 = project(P, d1, g1, sp, cp, st1, ct1, nRows, nCols, half_nRows, angle_res_inv, C);
-        project_fix(o0, nRows, nCols, half_nRows, angle_res_inv);
-        project_fix(o1, nRows, nCols, half_nRows, angle_res_inv);
-        const float4 G0 = tg[o0.t], G1 = tg[o1.t];
-        const float2 T0 = trg[o0.t], T1 = trg[o1.t];
-        contribute<METHOD, OCC>(A, o0, G0, T0, fl0, angle_res_inv, C);
-        contribute<METHOD, OCC>(A, o1, G1, T1, fl1, angle_res_inv, C);
-    };
     const int stride = gridDim.x * TPB;
-    if (PF == 1) {
-        // large levels: 4-pixel units (vector loads), processed as two pixel pairs (ILP)
-        for (int u = bidx * TPB + tidx; u < units; u += stride) {
-            const int r = u / cq;
-            const int c4 = u - r * cq;
-            const float4 a = src4[2 * u], b = src4[2 * u + 1];  // {g0,d0,g1,d1} {g2,d2,g3,d3}
-            const float4 s = st4[c4], c = ct4[c4];
-            const float sp = sinphi[r], cp = cosphi[r];
-            two(a.y, a.x, a.w, a.z, sp, cp, s.x, c.x, s.y, c.y, flag(4 * u), flag(4 * u + 1));
-            two(b.y, b.x, b.w, b.z, sp, cp, s.z, c.z, s.w, c.w, flag(4 * u + 2), flag(4 * u + 3));
-        }
-    } else if (PF == 2) {
-        // software-pipelined pixel stream, one wave = 64 consecutive pixels of one row (nCols % 64 == 0,
-        // so row/column come from wave-uniform scalar arithmetic and the row LUT is wave-uniform): while
-        // chunk k is accumulated, chunk k+1's target gathers and chunk k+2's source loads are in flight
-        const int npx = nRows * nCols;
-        const int lane = tidx & 63;
-        struct Src { float d, g, sp, cp, st, ct; int f; };
-        auto ld = [&](int base) {                          // base: wave-uniform first pixel
-            const int r = __builtin_amdgcn_readfirstlane(base / nCols);
-            const int c = base - r * nCols + lane;
-            const float2 a = src[base + lane];
-            return Src{a.y, a.x, sinphi[r], cosphi[r], sinth[c], costh[c], flag(base + lane)};
-        };
-        const Gather gt{__builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(tg), 0, npx * 16, 0x00020000),
-                        __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(trg), 0, npx * 8, 0x00020000)};
-        const int b0 = __builtin_amdgcn_readfirstlane((bidx * TPB + (tidx & ~63)));
-        if (b0 < npx) {
-            // Unrolled by two with fixed register roles (A, B) and unconditional loads (the chunk index is
-            // clamped to the wave's last chunk): no loop-carried copies of in-flight loads and the same
-            // number of loads on every path, so each wait names exactly the loads it needs.
-            const int n_it = (npx - 1 - b0) / stride + 1;  // chunks of this wave (>= 1)
-            auto base = [&](int k) { return b0 + (k < n_it ? k : n_it - 1) * stride; };
-            auto prj = [&](const Src& x) {
-                return project(P, x.d, x.g, x.sp, x.cp, x.st, x.ct, nRows, nCols, half_nRows, angle_res_inv, C);
-            };
-            // Per half-iteration h: load the source of chunk h+2, project chunk h+1 and issue its gathers,
-            // accumulate chunk h.  Loads are issued in the order they are consumed, so the in-order
-            // vmcnt lets each wait skip the five younger loads still in flight.
-            // The gathers of a chunk are issued speculatively from the fast projection; the rare
-            // guard-band lanes are re-projected at the next half-iteration boundary and, if a pixel
-            // changed, the chunk's gathers are re-issued before it is accumulated.
-            Src sA = ld(base(0));
-            Src sB = ld(base(1));
-            Proj oA = prj(sA);
-            int fA = sA.f;
-            project_fix(oA, nRows, nCols, half_nRows, angle_res_inv);
-            float4 GA = gt.g(oA.t);
-            float2 TA = gt.T(oA.t);
-            for (int k = 0;; k += 2) {
-                sA = ld(base(k + 2));
-                Proj oB = prj(sB);
-                const int fB = sB.f;
-                float4 GB = gt.g(oB.t);
-                float2 TB = gt.T(oB.t);
-                contribute<METHOD, OCC>(A, oA, GA, TA, fA, angle_res_inv, C);
-                if (k + 1 >= n_it) break;
-                if (project_fix(oB, nRows, nCols, half_nRows, angle_res_inv)) { GB = gt.g(oB.t); TB = gt.T(oB.t); }
-                sB = ld(base(k + 3));
-                oA = prj(sA);
-                fA = sA.f;
-                GA = gt.g(oA.t);
-                TA = gt.T(oA.t);
-                contribute<METHOD, OCC>(A, oB, GB, TB, fB, angle_res_inv, C);
-                if (k + 2 >= n_it) break;
-                if (project_fix(oA, nRows, nCols, half_nRows, angle_res_inv)) { GA = gt.g(oA.t); TA = gt.T(oA.t); }
-            }
-        }
-    } else if (PF == 3) {
-        // PF 2's pipelined wave stream with the guard-band lanes DEFERRED instead of fixed in place: a
+    if (PF == 3) {
+        // Software-pipelined pixel stream, one wave = 64 consecutive pixels of one row (nCols % 64 == 0, so row /
+        // column come from wave-uniform scalar arithmetic and the row LUT is wave-uniform): while chunk k is
+        // accumulated, chunk k+1's target gathers and chunk k+2's source loads are in flight.  Unrolled by two with
+        // fixed register roles (A, B) and unconditional loads (the chunk index is clamped to the wave's last chunk):
+        // no loop-carried copies of in-flight loads and the same number of loads on every path, so each wait names
+        // exactly the loads it needs.  The guard-band lanes are DEFERRED, not fixed in place: a
         // lane whose fast projection lands near a rounding boundary drops out of its chunk (no
         // contribution) and its pixel index goes to the wave's queue in global memory (room for every
         // pixel of the wave, so it never overflows); after the stream the wave runs the exact
@@ -925,11 +684,7 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
             }
         };
         const int b0 = __builtin_amdgcn_readfirstlane((bidx * TPB + (tidx & ~63)));
-#ifdef R360_EXP_NOLOOP   // experiment builds only: the pass without its pixel loop (fixed costs)
-        if (false) {
-#else
         if (b0 < npx) {
-#endif
             const int n_it = (npx - 1 - b0) / stride + 1;
             auto base = [&](int k) { return b0 + (k < n_it ? k : n_it - 1) * stride; };
             Src sA = ld(base(0));
@@ -958,9 +713,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                 if (k + 2 >= n_it) break;
             }
         }
-#ifdef R360_EXP_NODRAIN   // experiment builds only: deferred lanes dropped
-        qn = 0;
-#endif
         if (qn > 0) {
             // the queue was written by other lanes of this wave: order those stores before the reads
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -976,23 +728,21 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                 acc(o, gt.g(o.t), gt.T(o.t), act ? flag(i) : 0);
             }
         }
-    } else if (PF == 4 || PF == 5) {
+    } else if (PF == 5) {
         // PF 3's wave stream over the level's COMPACTED source points (LevelBufs::pts, built once per frame):
         // only pixels with minDepth < depth < maxDepth, as {LUT point, gray}, in raster order.  No row/column
         // tables, no LUT arithmetic and no lanes spent on pixels without depth.  Deferred lanes queue their
         // point index and are re-projected exactly after the stream.
-        // PF 5 (default): the same stream with contribute_lean's single-precision error terms and a contracted
-        // transform, and the deferred lanes of the workgroup's four waves drained together (a wave defers ~0.4 %
+        // The error terms are contribute_lean's (single precision) and the transform is contracted; the deferred
+        // lanes of the workgroup's four waves are drained together (a wave defers ~0.4 %
         // of its points, a few per pass: one drain chunk per workgroup instead of one mostly idle chunk per wave).
-        constexpr bool LEAN = PF == 5;
         const int nv = __builtin_amdgcn_readfirstlane(*npts);
         const int lane = tidx & 63;
         const int qcap = ((nv + stride - 1) / stride) * 64;
         int* q = dq + ((long)bidx * NW + (tidx >> 6)) * qcap;
         int qn = 0;
         auto acc = [&](const Proj& o, const float4 G, const float2 T) {
-            if (LEAN) contribute_lean<METHOD>(A, W, errf, o, G, T, angle_res_inv, C);
-            else contribute_fast<METHOD, 0>(A, W, o, G, T, 0, angle_res_inv, C);
+            contribute_lean<METHOD>(A, W, errf, o, G, T, angle_res_inv, C);
         };
         const Gather gt{__builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(tg), 0, nRows * nCols * 16, 0x00020000),
                         __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(trg), 0, nRows * nCols * 8, 0x00020000)};
@@ -1013,9 +763,9 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
             // (tests/test_gpu_icp_shapes.py).  PF 5 is the form of every level below 64 columns, lone or batched; the
             // image forms (PF 6 / 8 / 9, levels of 64 columns and more) keep the lean transform throughout.
             const Lut3 l{x.p.x, x.p.y, x.p.z, x.valid};
-            if (LEAN && nv < R360_EXACT_BELOW)
+            if (nv < R360_EXACT_BELOW)
                 return project_fast<false>(P, l, x.p.w, nRows, nCols, angle_res_inv, asin_out);
-            return project_fast<LEAN>(P, l, x.p.w, nRows, nCols, angle_res_inv, asin_out);
+            return project_fast<true>(P, l, x.p.w, nRows, nCols, angle_res_inv, asin_out);
         };
         auto defer = [&](Proj& o, int base) {
             const unsigned long long m = __ballot(o.fix);
@@ -1058,47 +808,31 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                 if (k + 2 >= n_it) break;
             }
         }
-        if (!LEAN && qn > 0) {
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-            for (int s0 = 0; s0 < qn; s0 += 64) {
-                const bool act = s0 + lane < qn;
-                const int i = act ? q[s0 + lane] : 0;
-                const float4 a = pts[i];
-                Proj o = project_exact(P, Lut3{a.x, a.y, a.z, true}, a.w, nRows, nCols, half_nRows, angle_res_inv);
-                o.vis = o.vis && act;
-                o.t = o.vis ? o.t : 0;
-                acc(o, gt.g(o.t), gt.T(o.t));
-            }
-        }
-        if (LEAN) {
-            // the workgroup's queues as one list (wave w's entries after those of waves < w), 64 entries per
-            // drain chunk, chunk j on wave j % NW; the queue stores of other waves are ordered before the loads
-            // by the workgroup-scope release / acquire of the barrier (one CU, one L1)
-            if (lane == 0) s_qn[tidx >> 6] = qn;
-            __syncthreads();
-            int pre[NW + 1];
-            pre[0] = 0;
+        // the workgroup's queues as one list (wave w's entries after those of waves < w), 64 entries per
+        // drain chunk, chunk j on wave j % NW; the queue stores of other waves are ordered before the loads
+        // by the workgroup-scope release / acquire of the barrier (one CU, one L1)
+        if (lane == 0) s_qn[tidx >> 6] = qn;
+        __syncthreads();
+        int pre[NW + 1];
+        pre[0] = 0;
 #pragma unroll
-            for (int w = 0; w < NW; ++w) pre[w + 1] = pre[w] + s_qn[w];
-            const int tot = pre[NW];
-            const int* qb = dq + (long)bidx * NW * qcap;
-            for (int s0 = (tidx >> 6) * 64; s0 < tot; s0 += NW * 64) {
-                const int g = s0 + lane;
-                const bool act = g < tot;
-                int w = 0;
+        for (int w = 0; w < NW; ++w) pre[w + 1] = pre[w] + s_qn[w];
+        const int tot = pre[NW];
+        const int* qb = dq + (long)bidx * NW * qcap;
+        for (int s0 = (tidx >> 6) * 64; s0 < tot; s0 += NW * 64) {
+            const int g = s0 + lane;
+            const bool act = g < tot;
+            int w = 0;
 #pragma unroll
-                for (int v = 1; v < NW; ++v) w += g >= pre[v] ? 1 : 0;
-                const int i = act ? qb[w * qcap + (g - pre[w])] : 0;
-                const float4 a = pts[i];
-                Proj o = project_exact(P, Lut3{a.x, a.y, a.z, true}, a.w, nRows, nCols, half_nRows, angle_res_inv);
-                o.vis = o.vis && act;
-                o.t = o.vis ? o.t : 0;
-                acc(o, gt.g(o.t), gt.T(o.t));
-            }
+            for (int v = 1; v < NW; ++v) w += g >= pre[v] ? 1 : 0;
+            const int i = act ? qb[w * qcap + (g - pre[w])] : 0;
+            const float4 a = pts[i];
+            Proj o = project_exact(P, Lut3{a.x, a.y, a.z, true}, a.w, nRows, nCols, half_nRows, angle_res_inv);
+            o.vis = o.vis && act;
+            o.t = o.vis ? o.t : 0;
+            acc(o, gt.g(o.t), gt.T(o.t));
         }
-    } else if (PF == 6 || PF == 10) {
-        // (PF 10, experiment builds: the same body without the two-chunk software pipeline, at R360_PF10_MINB waves per
-        // SIMD: latency hidden by more waves instead of a second chunk in flight)
+    } else if (PF == 6) {
         // Level 0 from the PACKED level-0 images (LevelBufs::pk, 4 B per pixel: range mm | luma << 16): the
         // source is streamed as the image itself, one wave = 64 consecutive pixels of one row (nCols % 64 == 0),
         // and the target {gray, depth} is gathered from the target's packed image (4 B instead of 8).  Per pass
@@ -1118,31 +852,13 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(J.tpk), 0, npx * 4, 0x00020000);
         auto gray_of = [](unsigned v) { return (float)(v >> 16) * (float)(1. / 255); };   // k_stitch4's expressions
         auto depth_of = [](unsigned v) { return (float)(v & 0xffffu) * 0.001f; };
-#ifdef R360_EXP_NOGATHER   // experiment builds only (tools/exp_variants.sh): no target loads
-        auto gG = [&](int t) { const float v = (float)(t & 1023) * 1e-3f; return make_float4(v, -v, v, 0.5f * v); };
-        auto gT = [&](int t) { return (unsigned)(t & 0xffffff); };
-#else
         auto gG = [&](int t) {
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_g, t * 16, 0, 0);
             return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
         };
         auto gT = [&](int t) { return __builtin_amdgcn_raw_buffer_load_b32(rs_t, t * 4, 0, 0); };
-#endif
-#if R360_PK_ACC
-        AccPk K;
-        pk_zero(K);
-#endif
         auto acc = [&](const Proj& o, const float4 G, unsigned tv) {
-#ifdef R360_EXP_NOACC   // experiment builds only: keep the operands alive, skip the math
-            A.h[0] += o.vis ? G.x + G.y + G.z + G.w + gray_of(tv) + depth_of(tv) + o.X + o.dist : 0.f;
-            W.c28 += wave_count(o.vis);
-            return;
-#endif
-#if R360_PK_ACC
-            contribute_pk<METHOD>(K, W, errf, o, G, make_float2(gray_of(tv), depth_of(tv)), angle_res_inv, C);
-#else
             contribute_lean<METHOD, false>(A, W, errf, o, G, make_float2(gray_of(tv), depth_of(tv)), angle_res_inv, C);
-#endif
         };
         // row of a wave-uniform pixel index: a float estimate corrected by one step either way (exact for
         // pixel indices below 2^24, every level-0 size here)
@@ -1190,30 +906,16 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                 qn += __popcll(m);
             }
         };
-        const int nbx = (int)gridDim.x;   // XCD-aware stream order (as PF 4 / 5)
+        const int nbx = (int)gridDim.x;   // XCD-aware stream order (as PF 5)
         const int bx = (nbx & 7) ? (int)bidx : ((int)bidx & 7) * (nbx >> 3) + ((int)bidx >> 3);
         const int b0 = __builtin_amdgcn_readfirstlane((bx * TPB + (tidx & ~63)));
-#ifdef R360_EXP_NOLOOP   // experiment builds only: the pass without its pixel loop (fixed costs)
-        if (false) {
-#else
         if (b0 < npx) {
-#endif
             const int n_it = (npx - 1 - b0) / stride + 1;
             n_it_ = n_it;
             cur_i = b0;
             cur_r = __builtin_amdgcn_readfirstlane(row_of(b0));
             cur_c = b0 - cur_r * nCols;
             auto base = [&](int k) { return b0 + (k < n_it ? k : n_it - 1) * stride; };
-            if constexpr (PF == 10) {
-                for (int k = 0; k < n_it; ++k) {
-                    const Src sx = ld();
-                    Proj ox = prj(sx);
-                    defer(ox, base(k));
-                    const float4 Gx = gG(ox.t);
-                    const unsigned Tx = gT(ox.t);
-                    acc(ox, Gx, Tx);
-                }
-            } else {
             Src sA = ld();
             Src sB = ld();
             Proj oA = prj(sA);
@@ -1235,7 +937,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                 TA = gT(oA.t);
                 acc(oB, GB, TB);
                 if (k + 2 >= n_it) break;
-            }
             }
         }
         // the workgroup's deferred lanes, drained together (as PF 5)
@@ -1262,9 +963,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
             o.t = o.vis ? o.t : 0;
             acc(o, gG(o.t), gT(o.t));
         }
-#if R360_PK_ACC
-        pk_fold(A, K);
-#endif
     } else if (PF == 8 || PF == 9) {
         // Coarse levels of batched launches from the level's {gray, depth} IMAGE instead of the source's compacted
         // points (round 6): frames that only enter batches then skip the per-frame source compaction (two launches per
@@ -1346,7 +1044,7 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
                 qn += __popcll(m);
             }
         };
-        const int nbx = (int)gridDim.x;   // XCD-aware stream order (as PF 4 / 5 / 6)
+        const int nbx = (int)gridDim.x;   // XCD-aware stream order (as PF 5 / 6)
         const int bx = (nbx & 7) ? (int)bidx : ((int)bidx & 7) * (nbx >> 3) + ((int)bidx >> 3);
         const int b0 = __builtin_amdgcn_readfirstlane((bx * TPB + (tidx & ~63)));
         if (b0 < npx) {
@@ -1403,152 +1101,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
             o.t = o.vis ? o.t : 0;
             acc(o, gG(o.t), gT(o.t));
         }
-    } else if (PF == 7) {
-        // PF 6 with a deeper software pipeline (sources two steps ahead of their projection, gathers two steps
-        // ahead of their accumulation): the level-0 pass is bound by memory latency, not by VALU or bytes
-        // Level 0 from the PACKED level-0 images (LevelBufs::pk, 4 B per pixel: range mm | luma << 16): the
-        // source is streamed as the image itself, one wave = 64 consecutive pixels of one row (nCols % 64 == 0),
-        // and the target {gray, depth} is gathered from the target's packed image (4 B instead of 8).  Per pass
-        // and pair that reads 4 N + 20 V bytes instead of PF 5's 16 N_valid + 24 V, with the LUT point computed
-        // from the row / column tables by the compaction's own float expressions (lut_point) and gray / depth by
-        // the stitch's (luma * (float)(1/255), range * 0.001f): bit for bit the values PF 5 reads.  Pixels
-        // without a valid depth ride along as invisible lanes (~10 % at level 0).  Projection, lean terms and the
-        // workgroup drain as PF 5.
-        const int npx = nRows * nCols;
-        const int lane = tidx & 63;
-        const int qcap = ((npx + stride - 1) / stride) * 64;
-        int* q = dq + ((long)bidx * NW + (tidx >> 6)) * qcap;
-        int qn = 0;
-        const uint32_t* __restrict__ spk = J.spk;
-        const auto rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(spk), 0, npx * 4, 0x00020000);
-        const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(tg), 0, npx * 16, 0x00020000);
-        const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(J.tpk), 0, npx * 4, 0x00020000);
-        auto gray_of = [](unsigned v) { return (float)(v >> 16) * (float)(1. / 255); };   // k_stitch4's expressions
-        auto depth_of = [](unsigned v) { return (float)(v & 0xffffu) * 0.001f; };
-#ifdef R360_EXP_NOGATHER   // experiment builds only (tools/exp_variants.sh): no target loads
-        auto gG = [&](int t) { const float v = (float)(t & 1023) * 1e-3f; return make_float4(v, -v, v, 0.5f * v); };
-        auto gT = [&](int t) { return (unsigned)(t & 0xffffff); };
-#else
-        auto gG = [&](int t) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_g, t * 16, 0, 0);
-            return make_float4(__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3]));
-        };
-        auto gT = [&](int t) { return __builtin_amdgcn_raw_buffer_load_b32(rs_t, t * 4, 0, 0); };
-#endif
-        auto acc = [&](const Proj& o, const float4 G, unsigned tv) {
-#ifdef R360_EXP_NOACC   // experiment builds only: keep the operands alive, skip the math
-            A.h[0] += o.vis ? G.x + G.y + G.z + G.w + gray_of(tv) + depth_of(tv) + o.X + o.dist : 0.f;
-            W.c28 += wave_count(o.vis);
-            return;
-#endif
-            contribute_lean<METHOD>(A, W, errf, o, G, make_float2(gray_of(tv), depth_of(tv)), angle_res_inv, C);
-        };
-        // row of a wave-uniform pixel index: a float estimate corrected by one step either way (exact for
-        // pixel indices below 2^24, every level-0 size here)
-        const float inv_cols = 1.f / (float)nCols;
-        auto row_of = [&](int i) {
-            int r = (int)((float)i * inv_cols);
-            r -= (r * nCols > i) ? 1 : 0;
-            r += ((r + 1) * nCols <= i) ? 1 : 0;
-            return r;
-        };
-        struct Src { unsigned v; float sp, cp, st, ct; };
-        auto ld = [&](int base) {                          // base: wave-uniform first pixel of a 64-pixel run
-            const int r = __builtin_amdgcn_readfirstlane(row_of(base));
-            const int c = base - r * nCols + lane;
-            return Src{__builtin_amdgcn_raw_buffer_load_b32(rs_s, (base + lane) * 4, 0, 0), sinphi[r], cosphi[r],
-                       sinth[c], costh[c]};
-        };
-        auto prj = [&](const Src& x) {
-            const float d = depth_of(x.v);
-            return project_fast<true>(P, lut_point(d, x.sp, x.cp, x.st, x.ct, C), gray_of(x.v), nRows, nCols,
-                                      angle_res_inv, asin_out);
-        };
-        auto defer = [&](Proj& o, int base) {
-            const unsigned long long m = __ballot(o.fix);
-            if (m) {
-                const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
-                                                                   __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if (o.fix) { q[pos] = base + lane; o.vis = false; o.t = 0; }
-                qn += __popcll(m);
-            }
-        };
-        const int nbx = (int)gridDim.x;   // XCD-aware stream order (as PF 4 / 5)
-        const int bx = (nbx & 7) ? (int)bidx : ((int)bidx & 7) * (nbx >> 3) + ((int)bidx >> 3);
-        const int b0 = __builtin_amdgcn_readfirstlane((bx * TPB + (tidx & ~63)));
-        if (b0 < npx) {
-            // three-step pipeline over chunk slots 0..2 (chunk h in slot h % 3, source slot (h + 1) % 3 refilled
-            // with chunk h + 4): each step loads the source of chunk h + 4, projects chunk h + 2 (its source
-            // loaded two steps earlier) and issues its gathers, and accumulates chunk h (gathered two steps
-            // earlier).  A projected chunk keeps only its key {p', gray, target pixel}; |p'| and 1/|p'| are
-            // recomputed by the same expressions when it is accumulated.
-            const int n_it = (npx - 1 - b0) / stride + 1;
-            auto base = [&](int k) { return b0 + (k < n_it ? k : n_it - 1) * stride; };
-            struct Key { float X, Y, Z, g; int t; };   // t = target pixel, -1 when not visible
-            auto stage_b = [&](const Src& x, int k, Key& K, float4& G, unsigned& T) {
-                Proj o = prj(x);
-                if (k < n_it) defer(o, base(k));   // a clamped tail chunk is never accumulated
-                K = Key{o.X, o.Y, o.Z, o.gray_s, o.vis ? o.t : -1};
-                G = gG(o.t);
-                T = gT(o.t);
-            };
-            auto stage_c = [&](const Key& K, const float4 G, unsigned T) {
-                Proj o;
-                o.X = K.X; o.Y = K.Y; o.Z = K.Z; o.gray_s = K.g;
-                const float d2 = K.X * K.X + K.Y * K.Y + K.Z * K.Z;   // project_fast's expressions
-                o.dist_inv = __builtin_amdgcn_rsqf(d2);
-                o.dist = r360m::sqrt_rn(d2);
-                o.vis = K.t >= 0;
-                o.t = o.vis ? K.t : 0;
-                o.fix = false;
-                acc(o, G, T);
-            };
-            Src S0 = ld(base(0)), S1 = ld(base(1)), S2 = ld(base(2));
-            Key K0, K1, K2;
-            float4 G0, G1, G2;
-            unsigned T0, T1, T2;
-            stage_b(S0, 0, K0, G0, T0);
-            S0 = ld(base(3));
-            stage_b(S1, 1, K1, G1, T1);
-            for (int h = 0;; h += 3) {
-                S1 = ld(base(h + 4));
-                stage_b(S2, h + 2, K2, G2, T2);
-                stage_c(K0, G0, T0);
-                if (h + 1 >= n_it) break;
-                S2 = ld(base(h + 5));
-                stage_b(S0, h + 3, K0, G0, T0);
-                stage_c(K1, G1, T1);
-                if (h + 2 >= n_it) break;
-                S0 = ld(base(h + 6));
-                stage_b(S1, h + 4, K1, G1, T1);
-                stage_c(K2, G2, T2);
-                if (h + 3 >= n_it) break;
-            }
-        }
-        // the workgroup's deferred lanes, drained together (as PF 5)
-        if (lane == 0) s_qn[tidx >> 6] = qn;
-        __syncthreads();
-        int pre[NW + 1];
-        pre[0] = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) pre[w + 1] = pre[w] + s_qn[w];
-        const int tot = pre[NW];
-        const int* qb = dq + (long)bidx * NW * qcap;
-        for (int s0 = (tidx >> 6) * 64; s0 < tot; s0 += NW * 64) {
-            const int g = s0 + lane;
-            const bool act = g < tot;
-            int w = 0;
-#pragma unroll
-            for (int v = 1; v < NW; ++v) w += g >= pre[v] ? 1 : 0;
-            const int i = act ? qb[w * qcap + (g - pre[w])] : 0;
-            const unsigned v = spk[i];
-            const int r = i / nCols, c = i - r * nCols;
-            Proj o = project_exact(P, lut_point(depth_of(v), sinphi[r], cosphi[r], sinth[c], costh[c], C), gray_of(v),
-                                   nRows, nCols, half_nRows, angle_res_inv);
-            o.vis = o.vis && act;
-            o.t = o.vis ? o.t : 0;
-            acc(o, gG(o.t), gT(o.t));
-        }
     } else {
         // small levels: one pixel per thread, so the latency chain per thread is a quarter as long
         const int npx = nRows * nCols;
@@ -1580,25 +1132,12 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
     const int lane = tidx & 63, wid = tidx >> 6;
     if (PF >= 3 && lane == 0) { A.h[27] += (float)W.c27; A.h[28] += (float)W.c28; A.h[29] += (float)W.c29; }
     if (PF >= 5) A.err2 = (double)errf;
-#ifdef R360_EXP_NOEPI   // experiment builds only
-    if (A.h[0] == 1.2345f) S->dbg[7] = 1;
-    return PASS_ARRIVED;
-#endif
-#ifdef R360_EXP_NOBFLY   // experiment builds only
-    const float mine = A.h[lane & 31];
-    const double e2 = A.err2, e2d = A.err2d;
-#else
     const float mine = wave_reduce_scatter32(A.h, lane);
     const double e2 = wave_sum_d(A.err2);
     const double e2d = OCC ? wave_sum_d(A.err2d) : 0.0;
-#endif
     if ((lane & 1) == 0) s_red[wid][scatter_slot(lane)] = mine;
     if (lane == 0) { s_err[wid] = e2; s_errd[wid] = e2d; }
     __syncthreads();
-#ifdef R360_EXP_NOREC   // experiment builds only: no record, no ticket
-    if (s_red[0][0] == 1.2345f) S->dbg[7] = 1;
-    return PASS_ARRIVED;
-#endif
     if (tidx < 32) {
         double v;
         if (tidx == R360_SUM_ERR2) {
@@ -1614,28 +1153,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();
-#if R360_POLL
-#define R360_KPRE nullptr
-    // ---- stage 2: record flags; the job's last workgroup polls them, reduces all records and runs the GN step
-    // Every workgroup but the last stores this launch's sequence number (C.seq, unique per launch on the ctx)
-    // into its own flag word once its record is drained (the sc1 record stores and the barrier as below); the
-    // last workgroup of the job (dispatched after all the others, so it waits only on workgroups that have
-    // started) reads the nb - 1 flags in parallel until every one holds C.seq.  No same-address
-    // atomics: the arrival ticket serialised 512 simultaneous arrivals at the memory side (a coarse level's
-    // workgroups all finish within a microsecond, and their ticket took ~12 us of the pass; profiles/r3_lone).
-    {
-        const int nb = (int)gridDim.x;
-        if ((int)bidx != nb - 1) {
-            if (tidx == 0)
-                __hip_atomic_store(gcnt + bidx, C.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return PASS_ARRIVED;
-        }
-        for (int b = tidx; b < nb - 1; b += TPB)
-            while (__hip_atomic_load(gcnt + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != C.seq)
-                __builtin_amdgcn_s_sleep(1);
-        __syncthreads();
-    }
-#else
     // ---- stage 2: arrival ticket; the last workgroup reduces all records and runs the GN step
     // Hand-off (MI355X_MICROARCH.md 'Valid forms', row 1): every record store is sc1 and drained by
     // its wave (vmcnt(0) above) before the barrier; one relaxed agent-scope add per workgroup; the
@@ -1644,7 +1161,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
     // Two-level ticket: agent-scope atomics on one address serialise at the memory side (~50 ns each,
     // 256 of them were ~13 us of every level-0 pass), so workgroups first count in 16 group counters
     // (4 KB apart) and only the last of each group takes the pass ticket: 32 + 16 deep instead of 512.
-#if R360_GROUP_SUM
     // Two-level record sum along the two-level ticket: the last workgroup of ticket group g (records g, g + 16,
     // ...) sums its group's records into a group record (slot nb + g) while other groups are still arriving, and
     // the last group's workgroup then sums only the 16 group records.  Group sum: thread (s, q) adds records
@@ -1681,7 +1197,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         kpre[2] = __hip_atomic_load(kt + 9 + lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         kpre[3] = __hip_atomic_load(kt + 18 + lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#define R360_KPRE kpre
     {
         const int g = (int)bidx % R360_TICKET_GROUPS;
         const int gsz = (nb - g + R360_TICKET_GROUPS - 1) / R360_TICKET_GROUPS;
@@ -1719,31 +1234,9 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
     if (!s_last) return PASS_ARRIVED;
     if (tidx < R360_TICKET_GROUPS)   // every group is complete: reset its counter for the next pass
         __hip_atomic_store(gcnt + tidx * R360_TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-#define R360_KPRE nullptr
-    if (tidx == 0) {
-        const int nb = (int)gridDim.x;
-        const int ng = nb < R360_TICKET_GROUPS ? nb : R360_TICKET_GROUPS;
-        const int g = (int)bidx % R360_TICKET_GROUPS;
-        const unsigned gsz = (unsigned)((nb - g + R360_TICKET_GROUPS - 1) / R360_TICKET_GROUPS);
-        const unsigned prev = __hip_atomic_fetch_add(gcnt + g * R360_TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int last = 0;
-        if (prev == gsz - 1) {
-            const unsigned p2 = __hip_atomic_fetch_add(&S->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = (p2 == (unsigned)ng - 1);
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return PASS_ARRIVED;
-    if (tidx < R360_TICKET_GROUPS)   // every group is complete: reset its counter for the next pass
-        __hip_atomic_store(gcnt + tidx * R360_TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-#endif
 #ifdef R360_STAMPS
     const unsigned long long t_ticket = __builtin_amdgcn_s_memrealtime();
 #endif
-#if !R360_POLL && R360_GROUP_SUM
     if (tidx < 16 * R360_TICKET_GROUPS) {   // the group records, 16 B per lane
         const int q = tidx & 15, g = tidx >> 4;
         double a0 = 0.0, a1 = 0.0;
@@ -1756,32 +1249,6 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         s_fin[g][2 * q] = a0;
         s_fin[g][2 * q + 1] = a1;
     }
-#else
-    {
-        // fixed-order reduction of the per-workgroup records: lane q of a 16-lane group loads bytes
-        // 16q..16q+15 of records g, g+RG, ... with L1-bypassing (sc1) 16-B buffer loads, 8 in flight;
-        // then thread v sums slot v over the groups in order
-        const int q = tidx & 15, g = tidx >> 4;
-        const int nb = (int)gridDim.x;
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(partials, 0, nb * 256, 0x00020000);
-        double a0 = 0.0, a1 = 0.0;
-        auto add = [&](const decltype(__builtin_amdgcn_raw_buffer_load_b128(rs, 0, 0, 16))& x) {
-            a0 += __longlong_as_double((long long)(((unsigned long long)x[1] << 32) | x[0]));
-            a1 += __longlong_as_double((long long)(((unsigned long long)x[3] << 32) | x[2]));
-        };
-        int r = g;
-        for (; r + 7 * RG < nb; r += 8 * RG) {
-            decltype(__builtin_amdgcn_raw_buffer_load_b128(rs, 0, 0, 16)) x[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, ((r + j * RG) * 16 + q) * 16, 0, 16);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) add(x[j]);
-        }
-        for (; r < nb; r += RG) add(__builtin_amdgcn_raw_buffer_load_b128(rs, (r * 16 + q) * 16, 0, 16));
-        s_fin[g][2 * q] = a0;
-        s_fin[g][2 * q + 1] = a1;
-    }
-#endif
     __syncthreads();
     if (tidx < 32) {
         double t = 0.0;
@@ -1805,19 +1272,14 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
 #endif
         if (tidx == 0) {
             S->ticket = 0;
-            pass_arrive(kt, true, C.level, R360_KPRE);   // the job's last workgroup
+            pass_arrive(kt, true, C.level, kpre);   // the job's last workgroup
         }
         return PASS_STEPPED;
     }
     // Stage the whole state in LDS with one coalesced 16-B access per thread, run the step on the LDS copy (one
     // lane walking global memory serialises ~150 dependent accesses, ~35 us), then write it back the same way.
     uint4* sq = reinterpret_cast<uint4*>(&s_state);
-#if !R360_POLL && R360_GROUP_SUM
     if ((int)tidx < NQ) sq[tidx] = st_q;   // loaded with the group records
-#else
-    constexpr int NQ = (int)(sizeof(IcpState) / 16);
-    for (int q = tidx; q < NQ; q += TPB) sq[q] = reinterpret_cast<const uint4*>(S)[q];
-#endif
     __syncthreads();
     gn_step_block(&s_state, s_fin[0], C, first, &s_gn, tidx);
     if (tidx == 0) {
@@ -1853,19 +1315,15 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         if (PERSIST && gridDim.y > 1)   // a batched persistent level launch: its span is closed by the last exit
             __hip_atomic_fetch_add(kt + 18 + (C.level & 7), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else
-            pass_arrive(kt, true, C.level, R360_KPRE, PERSIST);
+            pass_arrive(kt, true, C.level, kpre, PERSIST);
     }
-#undef R360_KPRE
     return PASS_STEPPED;
 }
 
 // PF 9 (coarse levels whose rows do not split into whole waves: per-lane rows, one more table pair live) at 4 waves per
 // SIMD: at 5 its pipelined chunks spilled 20 B per lane; the levels it serves are the two smallest
 template <int METHOD, int PF, int TOP, int OCC>
-#ifndef R360_PF10_MINB
-#define R360_PF10_MINB 6
-#endif
-__global__ __launch_bounds__(TPB, PF == 9 ? 4 : PF == 10 ? R360_PF10_MINB : R360_ICP_MINB) void k_icp_pass(const IcpJobs jobs, const float* __restrict__ sinphi,
+__global__ __launch_bounds__(TPB, PF == 9 ? 4 : ICP_MINB) void k_icp_pass(const IcpJobs jobs, const float* __restrict__ sinphi,
                                                  const float* __restrict__ cosphi, const float* __restrict__ sinth,
                                                  const float* __restrict__ costh, int nRows, int nCols,
                                                  IcpConst C, int first, int eval_only,
@@ -1885,27 +1343,13 @@ __global__ __launch_bounds__(TPB, PF == 9 ? 4 : PF == 10 ? R360_PF10_MINB : R360
 // a full-grid dispatch whose workgroups exit at entry, 29 of a lone pair's 65 launches), and the ~3 us kernel
 // boundary of every pass becomes a one-flag hand-off.  base: the generation word at the launch start (every
 // workgroup reads it before its first arrival, and nothing is published before all have arrived).  Every wait
-// is bounded (R360_PERSIST_SPIN_TICKS): a timed-out waiter sets S->fault and leaves, and so do the others at
+// is bounded (PERSIST_SPIN_TICKS): a timed-out waiter sets S->fault and leaves, and so do the others at
 // their next wait, so the grid always drains.  The host launches it only when the grid fits one resident round
-// with a workgroup per CU to spare (icp_level_persist_grid) and no other persistent launch of the process is in
+// with a workgroup per CU to spare (icp_level_persist_ok) and no other persistent launch of the process is in
 // flight.
-#ifndef R360_PERSIST_SLEEP
-#define R360_PERSIST_SLEEP 2   // s_sleep between polls (units of 64 clocks)
-#endif
-#ifndef R360_PERSIST_SPIN_TICKS
-#define R360_PERSIST_SPIN_TICKS 50000000ull   // 0.5 s of the 100 MHz s_memrealtime clock
-#endif
-#if R360_POLL || defined(R360_EXP_NOEPI) || defined(R360_EXP_NOREC)
-#define R360_PERSIST_BUILT 0   // these experiment bodies have no step workgroup
-#else
-#define R360_PERSIST_BUILT 1
-#endif
-#ifndef R360_LEVEL_PF0
-#define R360_LEVEL_PF0 6   // the level-0 form of the persistent launch (experiment variant lpf7: PF 7's deeper pipeline)
-#endif
-#ifndef R360_LEVEL_MINB
-#define R360_LEVEL_MINB 3   // waves per SIMD: a lone pass puts 2 workgroups on a CU, so registers are free up to 3
-#endif
+constexpr int PERSIST_SLEEP = 2;   // s_sleep between polls (units of 64 clocks)
+constexpr unsigned long long PERSIST_SPIN_TICKS = 50000000ull;   // 0.5 s of the 100 MHz s_memrealtime clock
+constexpr int LEVEL_MINB = 3;   // waves per SIMD: a lone pass puts 2 workgroups on a CU, so registers are free up to 3
 // The level loop of a persistent launch, for job blockIdx.y (its own state, records, tickets and generation word).
 template <int METHOD, int PF, int TOP>
 __device__ __forceinline__ void icp_level_loop(const IcpJobs& jobs, const float* __restrict__ sinphi,
@@ -1939,8 +1383,8 @@ __device__ __forceinline__ void icp_level_loop(const IcpJobs& jobs, const float*
             } else {
                 const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
                 while (__hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != tag) {
-                    __builtin_amdgcn_s_sleep(R360_PERSIST_SLEEP);
-                    if (__builtin_amdgcn_s_memrealtime() - t0 > R360_PERSIST_SPIN_TICKS) { go = 0; break; }
+                    __builtin_amdgcn_s_sleep(PERSIST_SLEEP);
+                    if (__builtin_amdgcn_s_memrealtime() - t0 > PERSIST_SPIN_TICKS) { go = 0; break; }
                 }
                 if (!go) __hip_atomic_store(&S->fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
@@ -1952,45 +1396,12 @@ __device__ __forceinline__ void icp_level_loop(const IcpJobs& jobs, const float*
 }
 
 template <int METHOD, int PF, int TOP>
-__global__ __launch_bounds__(TPB, R360_LEVEL_MINB) void k_icp_level(const IcpJobs jobs, const float* __restrict__ sinphi,
+__global__ __launch_bounds__(TPB, LEVEL_MINB) void k_icp_level(const IcpJobs jobs, const float* __restrict__ sinphi,
                                                   const float* __restrict__ cosphi, const float* __restrict__ sinth,
                                                   const float* __restrict__ costh, int nRows, int nCols,
                                                   IcpConst C, int passes, unsigned long long* __restrict__ kt) {
     icp_level_loop<METHOD, PF, TOP>(jobs, sinphi, cosphi, sinth, costh, nRows, nCols, C, passes, kt);
 }
-
-// ---- batched persistent coarse levels (round 6, experiment builds: measured slower, see launch_icp_levels_batch): ONE
-// launch runs a coarse level of every job of a batch, each job on
-// its own R360_COARSE_WG workgroups looping over the level's 1 + maxIters passes with the hand-off above (per-job
-// generation word; a job that stops leaves the loop, so no launch is spent on converged passes).  Per batch that
-// replaces 4 x 11 per-pass launches (most exiting at entry once their jobs converged, each with its launch gap on the
-// dense stream, profiles/r6_s8) with 4.  A job's workgroups never wait on another job's, so the launch needs no
-// resident round: workgroups are dispatched in index order (x, then the job y), the earliest unfinished job's
-// workgroups are dispatched before any later job's, and each job's <= R360_COARSE_WG workgroups fit the GPU.  The
-// bounded waits of the hand-off stay as the guard (a timed-out job faults, its batch returns an error).  The last
-// workgroup to exit closes the launch's in-kernel span.  3 waves per SIMD: inside the level loop the pass keeps more
-// values live (158 VGPRs; at 4 / 5 waves it spilled 52 / 148 B per lane).
-#if R360_EXPERIMENTS
-template <int METHOD, int PF>
-__global__ __launch_bounds__(TPB, 3) void k_icp_levels_batch(
-        const IcpJobs jobs, const float* __restrict__ sinphi, const float* __restrict__ cosphi,
-        const float* __restrict__ sinth, const float* __restrict__ costh, int nRows, int nCols, IcpConst C, int passes,
-        unsigned long long* __restrict__ kt) {
-    icp_level_loop<METHOD, PF, 0>(jobs, sinphi, cosphi, sinth, costh, nRows, nCols, C, passes, kt);
-    if (threadIdx.x == 0) {
-        const unsigned long long total = (unsigned long long)gridDim.x * gridDim.y;
-        const unsigned long long prev = __hip_atomic_fetch_add(kt + 17, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (prev == total - 1) {
-            __hip_atomic_store(kt + 17, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int lv = C.level & 7;
-            const unsigned long long t0 = __hip_atomic_load(kt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-            __hip_atomic_fetch_add(kt + 1 + lv, t1 > t0 ? t1 - t0 : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(kt + 9 + lv, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-#endif
 
 // ---------------------------------------------------------------- occlusion variants (§8(f)1)
 // Per pass, before the fused pass and at the same pose:
@@ -2379,21 +1790,20 @@ extern "C" int r360_debug_block_stamps(unsigned long long* out, int n) {
 }
 #endif
 
-// The pass forms the product library holds (each covered by the parity suite): PF 6 at level 0 (TOP = 1) of batched
-// launches, PF 5 on the other levels and at level 0 of lone alignments (and where the packed image is not streamable), PF 3 / PF 0 for the occlusion
-// variants (PF 0 where rows do not split into whole waves).  PF 1 / 2 / 4 / 7 and the forced-form knobs exist only
-// in the experiment builds (R360_EXPERIMENTS, make exp).
+// The pass forms (each covered by the parity suite), as pass_grid picks them.  Plain pass: PF 6 at level 0 (TOP = 1)
+// of batched launches, PF 8 / 9 on their coarse levels of 64 columns and more, PF 5 on every level of a lone alignment
+// whose source has the level's compacted points and on every level below 64 columns.  Occlusion variants: PF 3, or
+// PF 0 where rows do not split into whole waves.  Any other form / occlusion pair has no kernel and is an error.
 template <int M, int PF>
 static int launch_pass(r360_ctx* ctx, int nb, int njobs, const IcpJobs& jobs, const LevelBufs& Ls,
                         const LevelTrig& T, const IcpConst& C, int first, int eval_only, bool top) {
     void (*kern)(const IcpJobs, const float*, const float*, const float*, const float*, int, int, IcpConst, int, int,
                  unsigned long long*, const uint8_t*) = nullptr;
     if (C.occ) {
-        // PF 4 / 5 / 6 (compacted or packed source) have no occlusion form: the occlusion flags are per source pixel
-        constexpr int PFO = PF >= 4 ? 3 : PF;
-        if constexpr (PFO == 0 || PFO == 3 || R360_EXPERIMENTS)
-            kern = C.occ == 1 ? k_icp_pass<M, PFO, 0, 1> : k_icp_pass<M, PFO, 0, 2>;
-    } else if constexpr (PF == 5 || R360_EXPERIMENTS) {
+        // the occlusion flags are per source pixel: only the image streams PF 0 / 3 have an occlusion form
+        if constexpr (PF == 0 || PF == 3)
+            kern = C.occ == 1 ? k_icp_pass<M, PF, 0, 1> : k_icp_pass<M, PF, 0, 2>;
+    } else if constexpr (PF == 5) {
         kern = top ? k_icp_pass<M, PF, 1, 0> : k_icp_pass<M, PF, 0, 0>;
     } else if constexpr (PF == 6) {
         kern = k_icp_pass<M, PF, 1, 0>;   // level 0 only
@@ -2457,9 +1867,6 @@ int ensure_batch(r360_ctx* ctx, int n, long n_pixels) {
 struct PassGrid { int pf, nb; };
 static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int njobs = 1, bool batched = false,
                           bool pts = false) {
-    // 4-pixel units on the large levels, one pixel per thread where that still fits one resident
-    // round (latency-bound small levels); R360_ICP_PF=0/1 forces one form (experiments)
-    static const int pf_env = R360_KNOB("R360_ICP_PF", -1);
     static const int cap_env = R360_KNOB("R360_ICP_CAP", -1);
     // one resident round: CUs x workgroups per CU of the launched form (grid-stride beyond it)
     static const int cus = [] {   // thread-safe one-time query (contexts may be driven from several threads)
@@ -2469,8 +1876,8 @@ static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int
         return n;
     }();
     const int npx = Ls.rows * Ls.cols;
-    // PF 4 (compacted source points) for the plain pass; the occlusion variants index their flags by source
-    // pixel and keep the image stream (PF 3 where rows split into whole waves)
+    // The occlusion variants index their flags by source pixel and stream the image: PF 3 where rows split into
+    // whole waves, else PF 0 (one pixel per thread).  The plain pass:
     // level 0 (the only level with a packed image) streams the packed images where rows split into whole waves, in
     // batched launches: PF 6 reads 0.64x PF 5's bytes with fewer instructions, which a full chip of waves turns into
     // throughput.  A lone alignment's pass (two workgroups per CU, latency-bound) runs PF 5 over the source's
@@ -2482,13 +1889,9 @@ static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int
     // the two compaction launches per frame).  A lone alignment keeps PF 5 where its source has the level's points
     // (pts), and streams the image where it has not.
     const bool pk_ok = Ls.pk != nullptr && Ls.cols % 64 == 0;
-    static const bool coarse_pf5 = R360_KNOB("R360_COARSE_PF5", 0) != 0;   // experiment builds: round 5's coarse form
-    const bool img_ok = !pk_ok && Ls.cols >= 64 && !coarse_pf5;
+    const bool img_ok = !pk_ok && Ls.cols >= 64;
     const int pf_img = pk_ok ? 6 : img_ok ? (Ls.cols % 64 == 0 ? 8 : 9) : 5;
-    const int pf_dflt = occ ? ((Ls.cols % 64 == 0) ? 3 : 0) : (batched || !pts ? pf_img : 5);
-    const bool env_ok = pf_env >= 0 && !(pf_env >= 4 && occ) && !((pf_env == 6 || pf_env == 7 || pf_env == 10) && !pk_ok) &&
-                        !(pf_env == 8 && Ls.cols % 64 != 0) && !(pf_env == 9 && Ls.cols < 64);
-    const int pf = R360_EXPERIMENTS && env_ok ? pf_env : pf_dflt;
+    const int pf = occ ? ((Ls.cols % 64 == 0) ? 3 : 0) : (batched || !pts ? pf_img : 5);
     // workgroups per job and pass: 2 per CU (one resident round holds occ_q.per[pf] per CU; a batched launch
     // fills the rest with other jobs, and fewer records per job shorten the reduction tail)
     // workgroups per job and pass: a fixed number per level size, never a function of the batch, so that a
@@ -2516,7 +1919,7 @@ static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int
     // CU slots (under the pipelines' load their first workgroups waited for slots, profiles/r5_trace) and sum fewer
     // records: +0.9 % in an A/B (profiles/r5_envab/pxt/, r5_prep2/pxt8/).  The grid still depends only on the level size.
     const int pxt = pxt_env > 0 ? pxt_env : (batched ? 8 : 1);
-    int nb = pf == 1 ? icp_blocks_for(npx) : (npx + TPB * pxt - 1) / (TPB * pxt);
+    int nb = (npx + TPB * pxt - 1) / (TPB * pxt);
     if (nb > cap) nb = cap;
     if (nb < 1) nb = 1;
     return {pf, nb};
@@ -2532,7 +1935,7 @@ void icp_pass_grid(const r360_ctx* ctx, const r360_frame* src, int level, int oc
     if (nb) *nb = G.nb;
 }
 
-// deferred-queue entries one job's PF 3 / PF 4 pass needs: per wave ceil(npx / stride) * 64
+// deferred-queue entries one job's pass needs (PF 3 and above): per wave ceil(npx / stride) * 64
 static long defer_need(int npx, int nb) {
     const long stride = (long)nb * TPB;
     return (long)nb * (TPB / 64) * (((npx + stride - 1) / stride) * 64);
@@ -2541,22 +1944,12 @@ static long defer_need(int npx, int nb) {
 static int launch_jobs(r360_ctx* ctx, const IcpJobs& jobs, int njobs, const LevelBufs& Ls, const LevelTrig& T,
                        int level, int method, const IcpConst& C0, int first, int eval_only, const PassGrid& G) {
     IcpConst C = C0;
-    if (++ctx->icp_seq == 0) ++ctx->icp_seq;   // the record flags start (and may stale) at 0
+    if (++ctx->icp_seq == 0) ++ctx->icp_seq;   // never 0
     C.seq = ctx->icp_seq;
     const char* name = level == 0 ? "k_icp_pass_L0" : "k_icp_pass";
     const int slot = timing_begin(ctx, name);
     const int pf = G.pf, nb = G.nb;
     const bool top = level == 0;
-#if R360_EXPERIMENTS
-#define R360_LAUNCH_EXP(M)                                                                               \
-        else if (pf == 1) rc = launch_pass<M, 1>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
-        else if (pf == 2) rc = launch_pass<M, 2>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
-        else if (pf == 4) rc = launch_pass<M, 4>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
-        else if (pf == 7) rc = launch_pass<M, 7>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
-        else if (pf == 10) rc = launch_pass<M, 10>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top);
-#else
-#define R360_LAUNCH_EXP(M)
-#endif
 #define R360_LAUNCH(M)                                                                                   \
     do {                                                                                                 \
         if (pf == 3) rc = launch_pass<M, 3>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top);      \
@@ -2564,7 +1957,6 @@ static int launch_jobs(r360_ctx* ctx, const IcpJobs& jobs, int njobs, const Leve
         else if (pf == 6) rc = launch_pass<M, 6>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
         else if (pf == 8) rc = launch_pass<M, 8>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
         else if (pf == 9) rc = launch_pass<M, 9>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top); \
-        R360_LAUNCH_EXP(M)                                                                               \
         else rc = launch_pass<M, 0>(ctx, nb, njobs, jobs, Ls, T, C, first, eval_only, top);              \
     } while (0)
     int rc = 0;
@@ -2572,7 +1964,6 @@ static int launch_jobs(r360_ctx* ctx, const IcpJobs& jobs, int njobs, const Leve
     else if (method == R360_DEPTH_CONSISTENCY) R360_LAUNCH(R360_DEPTH_CONSISTENCY);
     else R360_LAUNCH(R360_PHOTO_DEPTH);
 #undef R360_LAUNCH
-#undef R360_LAUNCH_EXP
     timing_end(ctx, slot);
     if (rc) return rc;
     R360_HIP(hipGetLastError());
@@ -2592,54 +1983,6 @@ int launch_icp_jobs(r360_ctx* ctx, const IcpJobs& jobs, int n, const r360_frame*
     return launch_jobs(ctx, jobs, n, Ls, geom->calib->trig[level], level, method, C, first, eval_only, G);
 }
 
-// ---- batched persistent coarse levels (k_icp_levels_batch, experiment builds only: R360_COARSE_PERSIST=1): at most
-// R360_COARSE_WG workgroups per job, PF 8 / 9.  Measured slower than the per-pass launches in the pipelined bench (1690.7 /
-// 1696.4 vs 1738.0 / 1739.0 pairs/s alternating, profiles/r6_s9): the levels' workgroups, resident at 3 waves per SIMD
-// and spinning between passes, hold CU slots the pipelines' frame and plane kernels wait for.  Returns 1 (launch the
-// level pass by pass) in the product library and whenever the level has no persistent batched form.
-int launch_icp_levels_batch(r360_ctx* ctx, const IcpJobs& jobs, int n, const r360_frame* geom, int level, int method,
-                            const IcpConst& C0, int passes) {
-#if !R360_EXPERIMENTS
-    (void)ctx; (void)jobs; (void)n; (void)geom; (void)level; (void)method; (void)C0; (void)passes;
-    return 1;
-#else
-    // R360_COARSE_WG: workgroups per job (1: no hand-off waits at all); R360_COARSE_MIN_LEVEL: the finest level run
-    // this way (the finer ones pass by pass)
-    static const int coarse_wg = R360_KNOB("R360_COARSE_WG", 64);
-    static const int coarse_min = R360_KNOB("R360_COARSE_MIN_LEVEL", 1);
-    static const bool persist = R360_KNOB("R360_COARSE_PERSIST", 0) != 0;
-    if (level == 0 || level < coarse_min || C0.occ || !persist || !R360_PERSIST_BUILT) return 1;
-    if (n < 1 || n > R360_MAX_BATCH) { r360_set_error("batched passes: %d jobs (1..%d)", n, R360_MAX_BATCH); return -2; }
-    const LevelBufs& Ls = geom->lv[level];
-    PassGrid G = pass_grid(ctx, Ls, 0, n, true);
-    if (G.pf != 8 && G.pf != 9) return 1;
-    if (G.nb > coarse_wg) G.nb = coarse_wg;
-    if (ctx->bdefer_cap < defer_need(Ls.rows * Ls.cols, G.nb)) {
-        r360_set_error("batched passes: deferred-pixel queues not sized for %d pixels", Ls.rows * Ls.cols);
-        return -1;
-    }
-    const LevelTrig& T = geom->calib->trig[level];
-    IcpConst C = C0;
-    if (++ctx->icp_seq == 0) ++ctx->icp_seq;
-    C.seq = ctx->icp_seq;
-    void (*kern)(const IcpJobs, const float*, const float*, const float*, const float*, int, int, IcpConst, int,
-                 unsigned long long*) = nullptr;
-    auto pick = [&](auto m) {
-        constexpr int M = decltype(m)::value;
-        kern = G.pf == 8 ? k_icp_levels_batch<M, 8> : k_icp_levels_batch<M, 9>;
-    };
-    if (method == R360_PHOTO_CONSISTENCY) pick(std::integral_constant<int, R360_PHOTO_CONSISTENCY>{});
-    else if (method == R360_DEPTH_CONSISTENCY) pick(std::integral_constant<int, R360_DEPTH_CONSISTENCY>{});
-    else pick(std::integral_constant<int, R360_PHOTO_DEPTH>{});
-    const int slot = timing_begin(ctx, "k_icp_levels");
-    hipLaunchKernelGGL(kern, dim3(G.nb, n), dim3(TPB), 0, ctx->stream, jobs, T.sinphi, T.cosphi, T.sinth, T.costh,
-                       Ls.rows, Ls.cols, C, passes, ctx->d_ktime);
-    timing_end(ctx, slot);
-    R360_HIP(hipGetLastError());
-    return 0;
-#endif
-}
-
 // ---- persistent level launch (k_icp_level): resident-round check and launch
 template <int M, int PF, int TOP>
 static int level_blocks_per_cu() {   // the occupancy query for the instantiation (one device model per process)
@@ -2654,7 +1997,7 @@ static int level_blocks_per_cu() {   // the occupancy query for the instantiatio
 static int level_blocks_per_cu(int method, int pf) {
     auto by = [&](auto m) {
         constexpr int M = decltype(m)::value;
-        return pf == 6 ? level_blocks_per_cu<M, R360_LEVEL_PF0, 1>() : level_blocks_per_cu<M, 5, 0>();
+        return pf == 6 ? level_blocks_per_cu<M, 6, 1>() : level_blocks_per_cu<M, 5, 0>();
     };
     if (method == R360_PHOTO_CONSISTENCY) return by(std::integral_constant<int, R360_PHOTO_CONSISTENCY>{});
     if (method == R360_DEPTH_CONSISTENCY) return by(std::integral_constant<int, R360_DEPTH_CONSISTENCY>{});
@@ -2662,7 +2005,6 @@ static int level_blocks_per_cu(int method, int pf) {
 }
 
 bool icp_level_persist_ok(r360_ctx* ctx, const r360_frame* src, int level, int method) {
-    if (!R360_PERSIST_BUILT) return false;
     const LevelBufs& Ls = src->lv[level];
     const PassGrid G = pass_grid(ctx, Ls, 0, 1, false, (src->compacted >> level) & 1u);
     if (G.pf != 5 && G.pf != 6) return false;   // the product forms of the plain pass
@@ -2681,7 +2023,7 @@ int launch_icp_level_persist(r360_ctx* ctx, const r360_frame* trg, const r360_fr
     const LevelBufs& Lt = trg->lv[level];
     const LevelTrig& T = src->calib->trig[level];
     const PassGrid G = pass_grid(ctx, Ls, 0, 1, false, (src->compacted >> level) & 1u);
-    if (C0.occ || (G.pf != 5 && G.pf != 6) || !R360_PERSIST_BUILT) {
+    if (C0.occ || (G.pf != 5 && G.pf != 6)) {
         r360_set_error("persistent level launch: plain pass forms only");
         return -1;
     }
@@ -2698,7 +2040,7 @@ int launch_icp_level_persist(r360_ctx* ctx, const r360_frame* trg, const r360_fr
                  unsigned long long*) = nullptr;
     auto pick = [&](auto m) {
         constexpr int M = decltype(m)::value;
-        kern = G.pf == 6 ? k_icp_level<M, R360_LEVEL_PF0, 1> : k_icp_level<M, 5, 0>;
+        kern = G.pf == 6 ? k_icp_level<M, 6, 1> : k_icp_level<M, 5, 0>;
     };
     if (method == R360_PHOTO_CONSISTENCY) pick(std::integral_constant<int, R360_PHOTO_CONSISTENCY>{});
     else if (method == R360_DEPTH_CONSISTENCY) pick(std::integral_constant<int, R360_DEPTH_CONSISTENCY>{});

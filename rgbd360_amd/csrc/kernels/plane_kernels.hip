@@ -4,7 +4,7 @@
 //   k_bil_*       pcl::FastBilateralFilter (sigma_s 10, sigma_r 0.05): splat / fused blur / slice
 //   k_dcm         depth-change map + distance-map init            (IntegralImageNormalEstimation)
 //   k_distmap     two-pass chamfer distance map, row bands with halos (exact below the 9.5 cap)
-//   k_normals     AVERAGE_3D_GRADIENT normals from exact window sums + plane offset d = p.n
+//   k_normals_sat AVERAGE_3D_GRADIENT normals from exact window sums + plane offset d = p.n
 //   CCL, plane fit, refinement, boundary trace and statistics: plane_seg.hip
 //
 // Every float expression is the oracle's (oracle/src/planes_oracle.cpp), compiled with
@@ -245,49 +245,9 @@ __global__ void __launch_bounds__(BIL_COLS) k_bil_splat(const PlaneBatch B, int 
 }
 
 
-template <int AX>
-__device__ __forceinline__ void d_bil_blur(float2* __restrict__ grids, long grid_cells, int src_slot, long sw, long sh,
-                           const int* __restrict__ zmm, int sd_max) {
-    const int s = blockIdx.y;
-    float bmin, bmax;
-    long sd;
-    bool over;
-    if (!bil_params(zmm, s, sd_max, bmin, bmax, sd, over)) return;
-    const long ncol = sw * sh, cells = sd * ncol;
-    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= cells) return;
-    const float2* src = grids + (long)s * 2 * grid_cells + (long)src_slot * grid_cells;
-    float2* dst = grids + (long)s * 2 * grid_cells + (long)(1 - src_slot) * grid_cells;
-    const long z = c / ncol, col = c - z * ncol, y = col / sw, x = col - y * sw;
-    const long o = AX == 0 ? 1 : (AX == 1 ? sw : ncol);
-    const long a0 = AX == 0 ? x : (AX == 1 ? y : z);           // coordinate along the axis
-    const long an = AX == 0 ? sw : (AX == 1 ? sh : sd);
-    const bool other_bnd = AX == 0 ? (y <= 0 || y >= sh - 1 || z <= 0 || z >= sd - 1)
-                                   : AX == 1 ? (x <= 0 || x >= sw - 1 || z <= 0 || z >= sd - 1)
-                                             : (x <= 0 || x >= sw - 1 || y <= 0 || y >= sh - 1);
-    if (other_bnd || a0 <= 0 || a0 >= an - 1) { dst[c] = make_float2(0.f, 0.f); return; }
-    // first iteration at axis offsets -1, 0, +1 (zero on the boundary)
-    float2 b1[3];
-#pragma unroll
-    for (int k = -1; k <= 1; ++k) {
-        const long ak = a0 + k;
-        if (ak <= 0 || ak >= an - 1) { b1[k + 1] = make_float2(0.f, 0.f); continue; }
-        const long q = c + k * o;
-        const float2 a = src[q - o], b = src[q + o], m = src[q];
-        b1[k + 1] = make_float2((a.x + b.x + 2.0f * m.x) / 4.0f, (a.y + b.y + 2.0f * m.y) / 4.0f);
-    }
-    dst[c] = make_float2((b1[0].x + b1[2].x + 2.0f * b1[1].x) / 4.0f, (b1[0].y + b1[2].y + 2.0f * b1[1].y) / 4.0f);
-}
-template <int AX>
-__global__ void k_bil_blur(const PlaneBatch B, long grid_cells, int src_slot, long sw, long sh, int sd_max) {
-    const PlaneDev& D = B.f[blockIdx.z];
-    d_bil_blur<AX>(D.grids, grid_cells, src_slot, sw, sh, D.zmm, sd_max);
-}
-
-
 // The three axis passes in one launch: a workgroup stages a BT_X x BT_Y x BT_Z tile of the splat grid with a 2-cell
 // halo in LDS, blurs along x over the tile's y / z halo, then along y over its z halo, then along z, and writes the
-// tile once (the three launches read and wrote the whole grid three times).  Every cell is computed by d_bil_blur's
+// tile once (the three launches read and wrote the whole grid three times).  Every cell is computed by a per-axis pass's
 // expressions from the same inputs, so the result is that of the three passes bit for bit; a halo cell outside the
 // grid is staged as zero and never enters an interior cell's value (a pass reads only in-grid neighbours of interior
 // cells, and every boundary cell of every pass is zero).
@@ -546,88 +506,7 @@ __device__ __forceinline__ void normal_out(const double (&gx)[3], const double (
     }
 }
 
-__device__ __forceinline__ void d_normals(const float4* __restrict__ cloud, const float* __restrict__ dist,
-                                                   int w, int h, float4* __restrict__ nrm) {
-    __shared__ float4 sdx[NT_SR * NT_SC], sdy[NT_SR * NT_SC];
-    const int s = blockIdx.z & 7;   // sensor (blockIdx.z / 8: the frame of the batch)
-    const int r0 = blockIdx.y * NT_R, c0 = blockIdx.x * NT_C;
-    const long N = (long)w * h;
-    const float4* P = cloud + (long)s * N;
-    // differences of the staged pixels (image rows r0 - NT_H .., columns c0 - NT_H ..); positions outside
-    // [1, h-2] x [1, w-2] are zero and counted, as the reference's border handling (never read by pixels that
-    // pass the 8-pixel border test)
-    for (int k = threadIdx.x; k < NT_SR * NT_SC; k += NT_TPB) {
-        const int yy = r0 - NT_H + k / NT_SC, xx = c0 - NT_H + k % NT_SC;
-        float4 a = make_float4(0.f, 0.f, 0.f, 1.f), b = a;
-        if (yy >= 1 && yy <= h - 2 && xx >= 1 && xx <= w - 2) {
-            const int q = yy * w + xx;
-            const float4 pr = P[q + 1], pl = P[q - 1], pu = P[q - w], pd = P[q + w];
-            const float dx0 = pr.x - pl.x, dx1 = pr.y - pl.y, dx2 = pr.z - pl.z;
-            const float dy0 = pd.x - pu.x, dy1 = pd.y - pu.y, dy2 = pd.z - pu.z;
-            a = isfin(dx0 + dx1 + dx2) ? make_float4(dx0, dx1, dx2, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-            b = isfin(dy0 + dy1 + dy2) ? make_float4(dy0, dy1, dy2, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        sdx[k] = a;
-        sdy[k] = b;
-    }
-    __syncthreads();
-    const float nan = __builtin_nanf("");
-    const int c = c0 + (threadIdx.x & (NT_C - 1));
-    for (int rr = threadIdx.x / NT_C; rr < NT_R; rr += NT_TPB / NT_C) {
-        const int r = r0 + rr;
-        if (r >= h || c >= w) continue;
-        const int j = r * w + c;
-        const long i = (long)s * N + j;
-        float4 o = make_float4(nan, nan, nan, nan);
-        const int border = 8;
-        const float4 p = P[j];
-        if (r >= border && r < h - border && c >= border && c < w - border && isfin(p.z)) {
-            const float dm = dist[i];
-            const float lim = 8.0f + p.z / 10.0f;
-            const float smoothing = dm < lim ? dm : lim;
-            if (smoothing > 2.0f) {
-                const int rs = (int)smoothing, rs2 = rs / 2;
-                const int sx = c - rs2, sy = r - rs2;
-                double gx[3] = {0, 0, 0}, gy[3] = {0, 0, 0};
-                unsigned cx = 0, cy = 0;
-                if (rs <= 2 * NT_H + 1) {
-                    float fcx = 0.f, fcy = 0.f;   // counts of <= 81 ones: exact in float
-                    for (int yy = sy; yy < sy + rs; ++yy) {
-                        const int rowb = (yy - (r0 - NT_H)) * NT_SC - (c0 - NT_H);
-                        for (int xx = sx; xx < sx + rs; ++xx) {
-                            const float4 a = sdx[rowb + xx], b = sdy[rowb + xx];
-                            gx[0] += a.x; gx[1] += a.y; gx[2] += a.z; fcx += a.w;
-                            gy[0] += b.x; gy[1] += b.y; gy[2] += b.z; fcy += b.w;
-                        }
-                    }
-                    cx = (unsigned)fcx;
-                    cy = (unsigned)fcy;
-                } else {
-                    for (int yy = sy; yy < sy + rs; ++yy)
-                        for (int xx = sx; xx < sx + rs; ++xx) {
-                            if (yy < 1 || yy > h - 2 || xx < 1 || xx > w - 2) { ++cx; ++cy; continue; }  // zero, finite
-                            const int q = yy * w + xx;
-                            const float4 a = P[q + 1], b = P[q - 1], u = P[q - w], d = P[q + w];
-                            const float dx0 = a.x - b.x, dx1 = a.y - b.y, dx2 = a.z - b.z;
-                            const float dy0 = d.x - u.x, dy1 = d.y - u.y, dy2 = d.z - u.z;
-                            if (isfin(dx0 + dx1 + dx2)) { gx[0] += dx0; gx[1] += dx1; gx[2] += dx2; ++cx; }
-                            if (isfin(dy0 + dy1 + dy2)) { gy[0] += dy0; gy[1] += dy1; gy[2] += dy2; ++cy; }
-                        }
-                }
-                normal_out(gx, gy, cx, cy, p, o);
-            }
-        }
-        nrm[i] = o;
-    }
-}
-__global__ void __launch_bounds__(NT_TPB) k_normals(const PlaneBatch B, int w, int h) {
-    const PlaneDev& D = B.f[blockIdx.z >> 3];
-    d_normals(D.cloud, D.dist, w, h, D.nrm);
-}
-
-
-
-// k_normals with the window sums read from summed-area tables of the staged tile instead of summed over the
+// The window sums are read from summed-area tables of the staged tile instead of summed over the
 // window: a table entry is a sum of at most (NT_SR x NT_SC) = 1728 central differences, each a multiple of 2^-36
 // below 2^5 in magnitude, so every entry (< 2^16) and every rectangle of entries is exact in double, and a window
 // sum S(y1,x1) - S(y0,x1) - S(y1,x0) + S(y0,x0) equals the direct sum bit for bit.  Per output pixel that is 4
@@ -686,7 +565,7 @@ __device__ __forceinline__ void d_normals_sat(const float4* __restrict__ cloud, 
                 a[u] = b[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (k < NS_H * NS_W && ty > 0 && tx > 0) {
                     const int yy = r0 - NT_H + ty - 1, xx = c0 - NT_H + tx - 1;
-                    st[u] = 1;   // outside [1, h-2] x [1, w-2]: zero and counted, as k_normals
+                    st[u] = 1;   // outside [1, h-2] x [1, w-2]: zero and counted (the reference's border handling)
                     if (yy >= 1 && yy <= h - 2 && xx >= 1 && xx <= w - 2) {
                         const int q = yy * w + xx;
                         a[u] = ph ? P[q + w] : P[q + 1];
@@ -764,7 +643,7 @@ __device__ __forceinline__ void d_normals_sat(const float4* __restrict__ cloud, 
         const float4 p = pt[j];
         if (rs_[j] > 0) {
             normal_out(g[0][j], g[1][j], cnt[0][j], cnt[1][j], p, o);
-        } else if (rs_[j] < 0) {   // window wider than the halo: summed from global memory as k_normals
+        } else if (rs_[j] < 0) {   // window wider than the halo: summed directly from global memory
             const float dm = dist[(long)s * N + r * w + c];
             const float lim = 8.0f + p.z / 10.0f;
             const int rs = (int)(dm < lim ? dm : lim), rs2 = rs / 2;
@@ -831,18 +710,10 @@ int launch_cloud_normals(const PlaneBatch& B, int F, const PlaneGeom& G, hipStre
         const long ncol = sw * sh;
         hipLaunchKernelGGL(k_bil_splat, dim3((ncol + BIL_COLS - 1) / BIL_COLS, 8, nf), dim3(BIL_COLS), 0, st, B, w, h,
                            sw, sh, G.sd_max, G.grid_cells);
-        // the three axis passes fused (k_bil_blur3; R360_BIL_FUSED=0, experiment builds: one launch per axis)
-        static const int fused = R360_KNOB("R360_BIL_FUSED", 1);
-        if (fused) {
-            const long ntile = ((sw + BT_X - 1) / BT_X) * ((sh + BT_Y - 1) / BT_Y);
-            hipLaunchKernelGGL(k_bil_blur3, dim3((unsigned)ntile, (unsigned)((G.sd_max + BT_Z - 1) / BT_Z), 8 * nf),
-                               dim3(BT_TPB), 0, st, B, G.grid_cells, sw, sh, G.sd_max);
-        } else {
-            const dim3 gb((unsigned)((ncol * G.sd_max + 255) / 256), 8, nf);
-            hipLaunchKernelGGL(k_bil_blur<0>, gb, dim3(256), 0, st, B, G.grid_cells, 0, sw, sh, G.sd_max);
-            hipLaunchKernelGGL(k_bil_blur<1>, gb, dim3(256), 0, st, B, G.grid_cells, 1, sw, sh, G.sd_max);
-            hipLaunchKernelGGL(k_bil_blur<2>, gb, dim3(256), 0, st, B, G.grid_cells, 0, sw, sh, G.sd_max);
-        }
+        // the three axis passes fused
+        const long ntile = ((sw + BT_X - 1) / BT_X) * ((sh + BT_Y - 1) / BT_Y);
+        hipLaunchKernelGGL(k_bil_blur3, dim3((unsigned)ntile, (unsigned)((G.sd_max + BT_Z - 1) / BT_Z), 8 * nf),
+                           dim3(BT_TPB), 0, st, B, G.grid_cells, sw, sh, G.sd_max);
         hipLaunchKernelGGL(k_bil_slice, dim3(blocks, 1, nf), dim3(256), 0, st, B, w, h, sw, sh, G.sd_max, G.grid_cells, 1);
     }
     timing_end(tctx, slot);
@@ -863,12 +734,9 @@ int launch_cloud_normals(const PlaneBatch& B, int F, const PlaneGeom& G, hipStre
     timing_end(tctx, slot);
     R360_HIP(hipGetLastError());
     slot = timing_begin(tctx, "k_normals");
-    // summed-area-table windows (default; R360_NORMALS_SAT=0: the direct window sums of k_normals); grid z = 8 sensors
-    // x the batch's frames
-    static const int nsat = R360_KNOB("R360_NORMALS_SAT", 1);
+    // summed-area-table windows; grid z = 8 sensors x the batch's frames
     const dim3 gn((w + NT_C - 1) / NT_C, (h + NT_R - 1) / NT_R, 8 * nf);
-    if (nsat) hipLaunchKernelGGL(k_normals_sat, gn, dim3(NT_TPB), 0, st, B, w, h);
-    else hipLaunchKernelGGL(k_normals, gn, dim3(NT_TPB), 0, st, B, w, h);
+    hipLaunchKernelGGL(k_normals_sat, gn, dim3(NT_TPB), 0, st, B, w, h);
     timing_end(tctx, slot);
     R360_HIP(hipGetLastError());
     return 0;

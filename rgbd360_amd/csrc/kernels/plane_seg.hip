@@ -2331,8 +2331,8 @@ int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int 
         const long slots = 8L * (h + w - 1) * h;
         hipLaunchKernelGGL(k_refine_skew, dim3((unsigned)((slots + 255) / 256), 1, nf), dim3(256), 0, st, B, w, h);
         const int tpb = 64 * ((h + 63) / 64);
-        // R360_REFINE_NARROW=0: the 64-bit mask path for every sensor (inspection)
-        static const int narrow_max = R360_KNOB("R360_REFINE_NARROW", 1) == 0 ? -1 : 30;
+        // a kernel argument kept for the argument layout: always 30 (-1 would take the 64-bit mask path for every sensor)
+        const int narrow_max = 30;
         if (rb == -1 && h <= 64 * RP_MAXB && w <= RP_MAXW) {
             if (h <= 256) {
                 hipLaunchKernelGGL((k_refine_pipe<1, 4>), dim3(8, 1, nf), dim3(tpb), 0, st, B, w, h, narrow_max);
@@ -2380,7 +2380,7 @@ int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int 
 template <bool MODEL>
 int launch_gm(int px, long total, const PlaneBatch& B, int F, hipStream_t st, int N) {
     const unsigned blocks = (unsigned)((total + px - 1) / px);
-    static const int exp = R360_KNOB("R360_EXP_GM", 0);   // timing experiments only
+    const int exp = 0;   // a kernel argument kept for the argument layout: always 0 (its other values cut work for timing)
     switch (px) {
 #define R360_GM_CASE(cpw)                                                                                         \
     case 256 * cpw:                                                                                               \

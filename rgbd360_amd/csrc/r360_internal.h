@@ -13,7 +13,7 @@
 
 #define R360_PI 3.14159265359  // include/Miscellaneous.h:44 (double literal)
 
-// Experiment knobs (pass forms, grid caps, CU masks, priorities, A/B switches) read the environment only in the
+// Experiment knobs (grid caps, queue depths, CU masks, priorities, host-side A/B switches) read the environment only in the
 // experiment builds (make exp / stamps, -DR360_EXPERIMENTS=1, lib/librgbd360_hip_exp.so): in the product library
 // R360_KNOB is its default and the variable's name is not even in the binary, so no environment variable can
 // change a registration.
@@ -97,7 +97,7 @@ struct IcpConst {
     double tol_res, tol_upd, lambda;
     int max_iters, fixed_iters0, n_pixels, level;
     int occ;                  // alignFrames360 occlusion: 0 plain, 1 Occ1, 2 Occ2 (:4598-4627)
-    unsigned seq;             // ICP pass: launch sequence number on the ctx (never 0), the record flags' value
+    unsigned seq;             // ICP pass: launch sequence number on the ctx (never 0); kept for the argument layout, no kernel reads it
 };
 
 // Device-resident Gauss-Newton state of one alignFrames360 call.
@@ -140,29 +140,21 @@ struct IcpJob {
     const float2* src;          // source level {gray, depth}
     const float2* trg;          // target level {gray, depth}
     const float4* tg;           // target level gradients
-    const float4* pts;          // source level compacted points (PF 4 / 5)
+    const float4* pts;          // source level compacted points (PF 5)
     const int* npts;            // their count
     const uint32_t* spk;        // level 0: source packed {range mm, luma} image (PF 6)
     const uint32_t* tpk;        // level 0: target packed image
     IcpState* S;
     double* partials;           // per-workgroup records
-    unsigned* gcnt;             // per-workgroup record flags (R360_POLL) / group arrival counters (16384 words)
+    unsigned* gcnt;             // group arrival counters (16384 words)
     int* dq;                    // deferred-pixel queues
 };
 struct IcpJobs { IcpJob j[R360_MAX_BATCH]; };   // passed by value (kernel arguments, 1152 B)
 
 constexpr int R360_KT_SLOTS = 26;
-#ifndef R360_GROUP_SUM   // 1: group records summed by each ticket group's last workgroup; 0 (experiment builds): flat sum
-#define R360_GROUP_SUM 1
-#endif
-#ifndef R360_POLL   // 0: arrival tickets; 1 (experiment builds): record flags polled by the job's last workgroup
-#define R360_POLL 0
-#endif
-#ifndef R360_TICKET_GROUPS_N   // experiment builds may regroup the same 16384 counter words
-#define R360_TICKET_GROUPS_N 16
-#endif
-constexpr int R360_TICKET_GROUPS = R360_TICKET_GROUPS_N;
-constexpr int R360_TICKET_STRIDE = 16384 / R360_TICKET_GROUPS_N;   // uints between group counters (4 KB at 16)
+// arrival tickets: a pass's workgroups count in 16 group counters, and each group's last workgroup sums its group's records
+constexpr int R360_TICKET_GROUPS = 16;
+constexpr int R360_TICKET_STRIDE = 16384 / R360_TICKET_GROUPS;   // uints between group counters (4 KB)
 // the persistent level launch's pass generation word: the last of the 16384 counter words, never a group counter
 constexpr int R360_PERSIST_FLAG_WORD = 16383;
 static_assert(R360_TICKET_STRIDE > 1, "the generation word must not be a group counter");
@@ -780,11 +772,8 @@ int launch_icp_jobs(r360_ctx* ctx, const IcpJobs& jobs, int n, const r360_frame*
 int icp_blocks_for(int n_pixels);
 // The persistent level launch (k_icp_level): all `passes` passes of a plain (C.occ == 0) lone alignment's level in
 // one launch.  icp_level_persist_ok: whether level's pass grid fits one resident round of that kernel with a
-// workgroup per CU to spare (and the build has it); launch_icp_level_persist enqueues it.
+// workgroup per CU to spare; launch_icp_level_persist enqueues it.
 bool icp_level_persist_ok(r360_ctx* ctx, const r360_frame* src, int level, int method);
-// a coarse level of a batch as one persistent launch (k_icp_levels_batch); 1 = no such form for it (launch per pass)
-int launch_icp_levels_batch(r360_ctx* ctx, const IcpJobs& jobs, int n, const r360_frame* geom, int level, int method,
-                            const IcpConst& C, int passes);
 int launch_icp_level_persist(r360_ctx* ctx, const r360_frame* trg, const r360_frame* src, int level, int method,
                              const IcpConst& C, int passes);
 // sizes ctx->d_defer for passes over up to n_pixels pixels (synchronises the ctx stream when it grows,

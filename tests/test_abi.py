@@ -153,7 +153,7 @@ def test_product_library_holds_only_covered_pass_forms_and_no_knobs():
     """The shipped library contains only the k_icp_pass forms the parity suite covers — PF 6 at level 0 of batched launches, PF 8 /
     PF 9 on their coarse levels, PF 5 on the coarse levels and at level 0 of lone alignments, PF 3 / PF 0 for the occlusion
     variants, for the three cost functions — and reads no experiment
-    knob from the environment (R360_ICP_PF / _CAP / _WG_TOTAL / _PXT, R360_DIAG_EXTRA_ITERS, ...: experiment builds
+    knob from the environment (R360_ICP_CAP / _WG_TOTAL / _PXT, R360_DIAG_EXTRA_ITERS, ...: experiment builds
     only, make exp), so no environment variable can change a registration."""
     blob = open(R.LIB_PATH, "rb").read()
     forms = set(re.findall(rb"k_icp_passILi([0-2])ELi([0-9])ELi([01])ELi([0-2])E", blob))

@@ -1,6 +1,6 @@
 """Micro-benchmark of the fused ICP pass at each pyramid level (eval mode, HIP-event timed).
-usage: R360_LIB=rgbd360_amd/lib/librgbd360_hip_exp.so python tools/icp_bench.py [reps]   (env R360_ICP_PF /
-R360_ICP_CAP select variants; experiment build only: make -C rgbd360_amd/csrc exp)"""
+usage: R360_LIB=rgbd360_amd/lib/librgbd360_hip_exp.so python tools/icp_bench.py [reps]   (env R360_ICP_CAP sets the
+grid cap; experiment build only: make -C rgbd360_amd/csrc exp)"""
 import os
 import sys
 
@@ -25,7 +25,7 @@ P = np.eye(4, dtype=np.float32)
 if os.environ.get("POSE") == "path":   # the synthetic path's true relative motion between the two frames
     P0, P1 = (np.asarray(R.synth_path_pose(seed, i), dtype=np.float64).reshape(4, 4) for i in range(2))
     P = (np.linalg.inv(P0) @ P1).astype(np.float32)
-tag = f"PF={os.environ.get('R360_ICP_PF', 'dflt')} CAP={os.environ.get('R360_ICP_CAP', 'dflt')}"
+tag = f"CAP={os.environ.get('R360_ICP_CAP', 'dflt')}"
 for lv in [int(x) for x in os.environ.get("LEVELS", "0,1,2").split(",")]:
     for _ in range(3):
         reg.eval(lv, P, R.PHOTO_DEPTH)

@@ -1,14 +1,14 @@
 #!/bin/bash
 # Static instruction mix of the level-0 ICP pass's pixel loop (k_icp_pass<PHOTO_DEPTH, PF, 1, 0>, PF from the
-# environment, default 4): compiles icp_kernels.hip to gfx950 assembly and counts the instructions of the
+# environment: 5 or 6, default 6): compiles icp_kernels.hip to gfx950 assembly and counts the instructions of the
 # innermost loop.
-# usage: [PF=3] tools/isa_count.sh [extra hipcc flags]      (CPU only)
+# usage: [PF=5] tools/isa_count.sh [extra hipcc flags]      (CPU only)
 set -e
 cd "$(dirname "$0")/.."
 OUT=/tmp/r360_isa; mkdir -p $OUT
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -munsafe-fp-atomics -fno-slp-vectorize \
   --cuda-device-only -S "$@" -o $OUT/icp.s rgbd360_amd/csrc/kernels/icp_kernels.hip 2>/dev/null
-PF=${PF:-4} python3 - "$OUT/icp.s" <<'PY'
+PF=${PF:-6} python3 - "$OUT/icp.s" <<'PY'
 import collections, os, re, sys
 pf = os.environ["PF"]
 s = open(sys.argv[1]).read().split("\n")
