@@ -134,6 +134,13 @@ int  r360_frame_get_depth_m(r360_frame* f, float* depth8);
  * gradients with the alignFrames360 seam mask applied).  Any pointer may be NULL. */
 int  r360_frame_get_level(r360_frame* f, int level, int* rows, int* cols, float* gray, float* depth,
                           float* gx, float* gy, float* dgx, float* dgy);
+/* The saliency flags the pyramid build keeps per level-0 pixel for the level-0 ICP pass, which skips the gradient
+ * gather and the terms of a target pixel the reference would skip (thresSaliencyIntensity / thresSaliencyDepth):
+ * flags[i] bit 0 = !(|gx| < thr_int && |gy| < thr_int), bit 1 the same of the depth gradients with thr_depth, and the
+ * thresholds they were built for (the r360_icp_default_params values; NaN: the frame has none).  An alignment with
+ * thresholds at or above them uses the flags; one with lower thresholds does not, and is correct but slower.
+ * flags: sph_rows x sph_cols bytes, or NULL. */
+int  r360_frame_get_saliency(r360_frame* f, uint8_t* flags, float* thr_int, float* thr_depth);
 /* The level's compacted ICP source points (valid depth, raster order) as {x, y, z, gray} quadruples:
  * LUT_xyz_sphere (RegisterPhotoICP.h:4553-4587) and the gray value.  *n = their count; copies min(n, cap). */
 int  r360_frame_get_points(r360_frame* f, int level, float* xyzg, int cap, int* n);

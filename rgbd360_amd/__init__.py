@@ -309,6 +309,7 @@ _SIGS = [
     ("r360_frame_get_sphere", C.c_int, [_P, _P, _P]),
     ("r360_frame_get_depth_m", C.c_int, [_P, _P]),
     ("r360_frame_get_level", C.c_int, [_P, C.c_int, _IP, _IP, _P, _P, _P, _P, _P, _P]),
+    ("r360_frame_get_saliency", C.c_int, [_P, _P, _FP, _FP]),
     ("r360_frame_get_points", C.c_int, [_P, C.c_int, _FP, C.c_int, _IP]),
     ("r360_frame_get_sensor_level", C.c_int, [_P, C.c_int, C.c_int, _IP, _IP, _P, _P, _P, _P, _P, _P]),
     ("r360_icp_default_params", None, [C.POINTER(IcpParams)]),
@@ -1057,6 +1058,14 @@ class Frame360:
         _check(lib().r360_frame_get_level(self.h, level, C.byref(r), C.byref(c), *[_vptr(a) for a in arrs]),
                "get_level")
         return dict(zip(["gray", "depth", "gx", "gy", "dgx", "dgy"], arrs))
+
+    def saliency(self):
+        """Level 0's saliency flags (bit 0: intensity gradient, bit 1: depth gradient) as a (sph_rows, sph_cols) uint8
+        array, and the (intensity, depth) thresholds they were built for (NaN: the frame has none)."""
+        fl = np.zeros((self.sph_rows, self.sph_cols), np.uint8)
+        ti, td = C.c_float(), C.c_float()
+        _check(lib().r360_frame_get_saliency(self.h, _vptr(fl), C.byref(ti), C.byref(td)), "get_saliency")
+        return fl, (ti.value, td.value)
 
     def points(self, level: int) -> np.ndarray:
         """The level's compacted ICP source points: (n, 4) {x, y, z, gray} (valid depth, raster order)."""

@@ -831,7 +831,7 @@ int frame_level0_materialise(r360_frame* f) {
     // nothing to do for a full frame; a frame without a built sphere is refused by its reader's own check
     if ((b & R360_BUILT_LEVEL0) || !(b & R360_BUILD_SPHERE) || f->rows <= 0) return 0;
     if (bind_device(f->ctx->device)) return -1;
-    if (launch_stitch(f, false)) return -1;
+    if (launch_stitch(f, false, true)) return -1;   // lv[0].pk stays: it may carry the pyramid's saliency flags
     // waited for: the reader may run on another context's stream (an alignment of frames built elsewhere)
     R360_HIP(hipStreamSynchronize(f->ctx->stream));
     f->built |= R360_BUILT_LEVEL0;
@@ -927,6 +927,21 @@ extern "C" int r360_frame_get_level(r360_frame* f, int level, int* rows, int* co
     if (level == 0 && frame_level0_materialise(f)) return -1;
     const LevelBufs& L = f->lv[level];
     return copy_level(f, L.p0, L.tg, L.rows, L.cols, rows, cols, gray, depth, gx, gy, dgx, dgy);
+}
+
+extern "C" int r360_frame_get_saliency(r360_frame* f, uint8_t* flags, float* thr_int, float* thr_depth) {
+    CHECK_ARG(f, "null frame");
+    CHECK_ARG(f->built & R360_BUILD_PYRAMID, "pyramid not built");
+    CHECK_ARG(f->lv[0].pk, "the frame has no packed level-0 image");
+    if (thr_int) *thr_int = f->sal_int;
+    if (thr_depth) *thr_depth = f->sal_depth;
+    if (!flags) return 0;
+    const size_t n = (size_t)f->lv[0].rows * f->lv[0].cols;
+    R360_HIP(hipStreamSynchronize(f->ctx->stream));
+    std::vector<uint32_t> pk(n);
+    R360_HIP(hipMemcpy(pk.data(), f->lv[0].pk, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) flags[i] = (uint8_t)((pk[i] & R360_PK_SAL) >> 24);
+    return 0;
 }
 
 extern "C" int r360_frame_get_points(r360_frame* f, int level, float* xyzg, int cap, int* n) {
@@ -1027,6 +1042,7 @@ static int align_graph_launch(r360_ctx* ctx, const r360_frame* trg, const r360_f
     put(ctx->d_state); put(ctx->d_partials); put(ctx->d_gticket); put(ctx->d_defer);
     key.push_back((uintptr_t)ctx->defer_cap); key.push_back((uintptr_t)ctx->partials_cap); put(ctx->d_ktime);
     put(src->d_npts); put(src->calib);
+    key.push_back((uintptr_t)icp_pk_nosal(trg, p->thres_sal_int, p->thres_sal_depth));   // IcpJob::nosal of level 0
     {
         uintptr_t w[(sizeof(r360_icp_params) + sizeof(uintptr_t) - 1) / sizeof(uintptr_t)] = {};
         memcpy(w, p, sizeof(r360_icp_params));
@@ -1273,6 +1289,7 @@ int align360_batch_enqueue(r360_ctx* ctx, int n, r360_frame* const* trg, r360_fr
             J.src = src[j]->lv[l].p0; J.trg = trg[j]->lv[l].p0; J.tg = trg[j]->lv[l].tg;
             J.pts = src[j]->lv[l].pts; J.npts = src[j]->d_npts + l;
             J.spk = src[j]->lv[l].pk; J.tpk = trg[j]->lv[l].pk;
+            J.nosal = icp_pk_nosal(trg[j], p->thres_sal_int, p->thres_sal_depth); J.pad = 0;
             J.S = ctx->d_bstate + j;
             J.partials = ctx->d_bpartials + (size_t)j * 32 * ctx->partials_cap;
             J.gcnt = ctx->d_bgticket + (size_t)j * tk;
@@ -1428,6 +1445,7 @@ extern "C" int r360_icp_eval_batch(r360_ctx* ctx, int n, r360_frame* const* trg,
         J.src = src[j]->lv[level].p0; J.trg = trg[j]->lv[level].p0; J.tg = trg[j]->lv[level].tg;
         J.pts = src[j]->lv[level].pts; J.npts = src[j]->d_npts + level;
         J.spk = src[j]->lv[level].pk; J.tpk = trg[j]->lv[level].pk;
+        J.nosal = icp_pk_nosal(trg[j], p->thres_sal_int, p->thres_sal_depth); J.pad = 0;
         J.S = ctx->d_bstate + j;
         J.partials = ctx->d_bpartials + (size_t)j * 32 * ctx->partials_cap;
         J.gcnt = ctx->d_bgticket + (size_t)j * tk;

@@ -8,6 +8,7 @@
 //   k_prep_l0, k_prep_tail : the sphere's pyramid and gradients, the two above tiled through LDS
 // All but the last two are HBM-streaming, one thread per output pixel.  Compiled with -ffp-contract=off so each
 // float expression rounds exactly as the reference's scalar C++ does.
+#include <type_traits>
 #include "../r360_internal.h"
 
 namespace {
@@ -124,7 +125,7 @@ __global__ void k_stitch(const uint8_t* __restrict__ bgr8, const uint16_t* __res
         // setSourceFrame / setTargetFrame level 0: CV_RGB2GRAY on BGR data, /255; depth *0.001
         const int y = (b * 4899 + g * 9617 + r * 1868 + (1 << 13)) >> 14;
         p0[i] = make_float2((float)y * (float)(1. / 255), (float)dd * 0.001f);
-        pk[i] = dd | ((unsigned)y << 16);
+        if (pk) pk[i] = dd | ((unsigned)y << 16);
     }
 }
 
@@ -201,7 +202,7 @@ __global__ void k_stitch4(const uint8_t* __restrict__ bgr8, const uint16_t* __re
                                                                  dd4[2] | ((unsigned)dd4[3] << 16));
         *reinterpret_cast<float4*>(p0 + i0) = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
         *reinterpret_cast<float4*>(p0 + i0 + 2) = make_float4(o[2].x, o[2].y, o[3].x, o[3].y);
-        *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
+        if (pk) *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
     }
 }
 
@@ -211,7 +212,8 @@ __global__ void k_stitch4(const uint8_t* __restrict__ bgr8, const uint16_t* __re
 // 64 sensor rows (a line per byte).  The tile goes through LDS and is stored row-major as k_stitch4 stores it.  Per
 // pixel the expressions of k_stitch (the sensor pose loaded once per column, which is one sensor), bit for bit.
 // LEAN: only the packed level-0 image is stored (4 of the 17 bytes per pixel), for frames whose other level-0
-// outputs no kernel reads (frame_level0_lean; the full form runs again if one is asked for).
+// outputs no kernel reads (frame_level0_lean; the full form runs again if one is asked for, then with pk = null: the
+// packed image stays as it is, saliency flags included).
 constexpr int STT_R = 64, STT_C = 16;
 template <bool LEAN>
 __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bgr8, const uint16_t* __restrict__ depth8,
@@ -264,7 +266,7 @@ __global__ void __launch_bounds__(256) k_stitch_t(const uint8_t* __restrict__ bg
     unsigned pk4[4], px[12];
 #pragma unroll
     for (int e = 0; e < 4; ++e) pk4[e] = s_pk[c0 + e][tr];
-    *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
+    if (pk) *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
     if (LEAN) return;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -304,19 +306,18 @@ struct LvF2 {
     __device__ __forceinline__ cell raw(long i) const { return p[i]; }
     static __device__ __forceinline__ float2 val(cell v) { return v; }
 };
+// The luma is masked to its 8 bits: bits 24 / 25 of the word are the saliency flags (R360_PK_SAL_*), which k_prep_l0
+// may be storing while the word is read.
 struct LvPk {
     const uint32_t* p;
     typedef uint32_t cell;
     __device__ __forceinline__ cell raw(long i) const { return p[i]; }
     static __device__ __forceinline__ float2 val(cell v) {
-        return make_float2((float)(v >> 16) * (float)(1. / 255), (float)(v & 0xffffu) * 0.001f);
+        return make_float2((float)((v >> 16) & 0xffu) * (float)(1. / 255), (float)(v & 0xffffu) * 0.001f);
     }
-    __device__ __forceinline__ float g(long i) const { return (float)(p[i] >> 16) * (float)(1. / 255); }
-    __device__ __forceinline__ float d(long i) const { return (float)(p[i] & 0xffffu) * 0.001f; }
-    __device__ __forceinline__ float2 gd(long i) const {
-        const uint32_t v = p[i];
-        return make_float2((float)(v >> 16) * (float)(1. / 255), (float)(v & 0xffffu) * 0.001f);
-    }
+    __device__ __forceinline__ float g(long i) const { return val(p[i]).x; }
+    __device__ __forceinline__ float d(long i) const { return val(p[i]).y; }
+    __device__ __forceinline__ float2 gd(long i) const { return val(p[i]); }
 };
 
 // nimg images of R x C stored back to back (the sphere: 1; the per-sensor pyramids: 8)
@@ -439,10 +440,18 @@ constexpr int L0_SR = L0_TR + 2 * L0_HALO, L0_SC = L0_TC + 2 * L0_HALO;   // sta
 constexpr int L0_1R = L0_TR / 2 + 2, L0_1C = L0_TC / 2 + 2;               // level-1 pixels: the tile's and a ring of 1
 constexpr int L0_HR = 2 * L0_1R + 3;                                      // source rows under them
 
+// Saliency flags (the packed image only; pkw = in.p, or null for none): with each level-0 gradient the workgroup
+// stores the pixel's word again with bits 24 / 25 set from the gradient just computed, sal_p = !(|gx| < ti && |gy| <
+// ti), sal_d = !(|dgx| < td && |dgy| < td): contribute_lean's tests.  The level-0 pass (PF 6) reads them from the
+// target word it gathers anyway and runs the gradient gather and the terms only for flagged pixels.  The store races
+// with the halo loads of the neighbouring workgroups, which read the same words; that is safe because a word is an
+// aligned 32-bit store (a reader sees the old or the new word, never a mix), its low 24 bits do not change (they are
+// rewritten with the value just read) and every reader masks the flags off (LvPk::val, PF 6's gray_of).  Every pixel
+// of the image is stored, salient or not, so bits of an earlier build never survive.
 template <class IN>
 __global__ void __launch_bounds__(256) k_prep_l0(const IN in, int R, int C, float4* __restrict__ tg0,
                                                  float2* __restrict__ p1, float4* __restrict__ tg1, float min_d,
-                                                 float max_d) {
+                                                 float max_d, uint32_t* pkw, float ti, float td) {
     __shared__ typename IN::cell s0[L0_SR][L0_SC];   // as loaded (the packed image: 4 B), IN::val() on every read
     __shared__ float sh[L0_HR][L0_1C];
     __shared__ float2 s1[L0_1R][L0_1C];
@@ -468,6 +477,14 @@ __global__ void __launch_bounds__(256) k_prep_l0(const IN in, int R, int C, floa
                         IN::val(s0[lr + 1][lc]));
         }
         tg0[(long)gy * C + gx] = o;
+        if constexpr (std::is_same<typename IN::cell, uint32_t>::value) {
+            if (pkw) {
+                const bool sal_p = !(fabsf(o.x) < ti && fabsf(o.y) < ti);
+                const bool sal_d = !(fabsf(o.z) < td && fabsf(o.w) < td);
+                pkw[(long)gy * C + gx] = (s0[r + L0_HALO][c + L0_HALO] & R360_PK_VALUE) | (sal_p ? R360_PK_SAL_P : 0u) |
+                                         (sal_d ? R360_PK_SAL_D : 0u);
+            }
+        }
     }
     if (!p1) return;   // a one-level pyramid
     // level-1 pixel (Y0 - 1 + i, X0 - 1 + j): its source rows are the cells 2 i .. 2 i + 4, its source columns the
@@ -672,7 +689,7 @@ bool frame_level0_lean(const r360_frame* f) {
     return !f->compact_all && f->rows > 0 && f->lv[0].pk && f->lv[0].cols % 64 == 0;
 }
 
-int launch_stitch(r360_frame* f, bool lean) {
+int launch_stitch(r360_frame* f, bool lean, bool keep_pk) {
     const r360_calib* c = f->calib;
     const long n = (long)f->sph_rows * f->sph_cols;
     if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipStreamWaitEvent(f->ctx->stream, e, 0));   // a split upload's BGR copy
@@ -681,28 +698,31 @@ int launch_stitch(r360_frame* f, bool lean) {
         r360_set_error("lean stitch: the tiled form only");
         return -1;
     }
+    // a stitch that writes the packed image writes whole words: the frame has no saliency flags until launch_pyramid
+    uint32_t* pk = keep_pk ? nullptr : f->lv[0].pk;
+    if (pk) f->sal_int = f->sal_depth = __builtin_nanf("");
     if (f->sph_cols % STT_C == 0) {
         const dim3 grid((f->sph_cols / STT_C) * ((f->sph_rows + STT_R - 1) / STT_R));
         if (lean)
             hipLaunchKernelGGL(k_stitch_t<true>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
                                f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                                c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
-                               f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
+                               f->d_sph_depth, f->lv[0].p0, pk);
         else
             hipLaunchKernelGGL(k_stitch_t<false>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
                                f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                                c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
-                               f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
+                               f->d_sph_depth, f->lv[0].p0, pk);
     } else if (f->sph_cols % 4 == 0)
         hipLaunchKernelGGL(k_stitch4, dim3(grid_for(n / 4)), dim3(TPB), 0, f->ctx->stream, f->d_bgr, f->d_depth,
                            f->rows, f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                            c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
-                           f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
+                           f->d_sph_depth, f->lv[0].p0, pk);
     else
         hipLaunchKernelGGL(k_stitch, dim3(grid_for(n)), dim3(TPB), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
                            f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                            c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
-                           f->d_sph_depth, f->lv[0].p0, f->lv[0].pk);
+                           f->d_sph_depth, f->lv[0].p0, pk);
     timing_end(f->ctx, slot);
     R360_HIP(hipGetLastError());
     return 0;
@@ -819,6 +839,7 @@ int launch_sphere_level0(r360_frame* f) {
     // cvtColor(CV_RGB2GRAY) / 255 and convertTo(CV_32F, 0.001): the stitch kernel's level-0 expressions
     hipLaunchKernelGGL(k_sensor_level0, dim3(grid_for(n)), dim3(TPB), 0, f->ctx->stream, f->d_sph_bgr, f->d_sph_depth,
                        n, f->lv[0].p0, f->lv[0].pk);
+    f->sal_int = f->sal_depth = __builtin_nanf("");   // whole words: no saliency flags until launch_pyramid
     R360_HIP(hipGetLastError());
     return 0;
 }
@@ -838,12 +859,19 @@ int launch_pyramid(r360_frame* f) {
         float2* p1 = more ? f->lv[1].p0 : nullptr;
         float4* tg1 = more ? f->lv[1].tg : nullptr;
         const dim3 grid(((L0.rows + L0_TR - 1) / L0_TR) * ((L0.cols + L0_TC - 1) / L0_TC));
-        if (L0.pk)
+        if (L0.pk) {
+            // the packed image's saliency flags, for the default thresholds of an alignment (r360_icp_default_params);
+            // an alignment with lower ones passes every visible pixel to its heavy stage instead (icp_pk_nosal)
+            r360_icp_params dp;
+            r360_icp_default_params(&dp);
             hipLaunchKernelGGL(k_prep_l0<LvPk>, grid, dim3(256), 0, f->ctx->stream, LvPk{L0.pk}, L0.rows, L0.cols, L0.tg,
-                               p1, tg1, min_d, max_d);
-        else
+                               p1, tg1, min_d, max_d, L0.pk, dp.thres_sal_int, dp.thres_sal_depth);
+            f->sal_int = dp.thres_sal_int;
+            f->sal_depth = dp.thres_sal_depth;
+        } else {
             hipLaunchKernelGGL(k_prep_l0<LvF2>, grid, dim3(256), 0, f->ctx->stream, LvF2{L0.p0}, L0.rows, L0.cols, L0.tg,
-                               p1, tg1, min_d, max_d);
+                               p1, tg1, min_d, max_d, (uint32_t*)nullptr, 0.f, 0.f);
+        }
     }
     // launch 2: the levels below level 1 and their gradients, three per launch
     for (int l = 1; l + 1 < f->n_levels; l += 3) {

@@ -13,6 +13,13 @@
 // gradients {gx, gy, dgx, dgy} + 8 B target {gray, depth} gathered — the 8N + 24V algorithmic
 // bytes of SURVEY.md §8(d).  No Jacobian rows are materialised (the reference writes and
 // re-reads imgSize x 6 buffers, :2761-2767).
+//
+// The level-0 pass of batched launches (PF 6) is sparse: it streams the packed images (4 B per source pixel, 4 B
+// per visible target pixel) and gathers the 16-byte gradient record and runs the terms only for the visible
+// pixels whose saliency flag is set in the target word (the pixels the reference does not `continue` past), in
+// a second stage over a per-wave queue.  The flags are built with the frame for the default thresholds; an
+// alignment with lower thresholds, or against a frame without flags, is neither refused nor wrong: every
+// visible pixel then takes the second stage, which is slower than the dense form was.
 #include <cstdio>
 #include <type_traits>
 #include "../r360_internal.h"
@@ -841,16 +848,39 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         // the stitch's (luma * (float)(1/255), range * 0.001f): bit for bit the values PF 5 reads.  Pixels
         // without a valid depth ride along as invisible lanes (~10 % at level 0).  Projection, lean terms and the
         // workgroup drain as PF 5.
+        //
+        // SPARSE: the reference skips a projected pixel whose target intensity gradient is below the saliency
+        // threshold (with PHOTO_DEPTH the depth term too; DEPTH alone tests the depth gradient): such a pixel adds 0
+        // to H, g and the error and only counts as visible.  The target word carries the two tests' outcomes in
+        // bits 24 / 25 (k_prep_l0, frame_kernels.hip), so the pass runs in two stages:
+        //  * the STREAM stage, per 64-pixel chunk and software-pipelined as before: source word and tables, LUT point,
+        //    fast projection, guard-band lanes queued for the exact drain, the target WORD gathered (4 B), visible
+        //    lanes counted, and the lanes that are visible and flagged ("needed") appended to the wave's queue by
+        //    ballot / mbcnt.  No gradient gather (16 of the 20 gathered bytes) and no terms.
+        //  * the HEAVY stage, over the workgroup's needed entries in full 64-lane chunks: source word again, the same
+        //    project_fast<true> expressions (the same pixel, bit for bit), gradient and target word gathered,
+        //    contribute_lean unchanged.  Its own sal_p / sal_d tests still decide: the flags are a prefilter that may
+        //    mark too many pixels, never too few (IcpJob::nosal sets both for every pixel where the flags were built
+        //    for higher thresholds than the alignment's or are missing: correct, and slower than the dense form was).
+        // A pixel enters the wave's queue at most once, as a guard-band lane (from the queue's end downwards) or as a
+        // needed one (from its start upwards), so the queue's room for every pixel of the wave still suffices.  What
+        // enters which queue depends on the frames and the pose alone, and the queues are walked in a fixed order:
+        // a job's sums do not depend on the batch it runs in.
         const int npx = nRows * nCols;
         const int lane = tidx & 63;
         const int qcap = ((npx + stride - 1) / stride) * 64;
         int* q = dq + ((long)bidx * NW + (tidx >> 6)) * qcap;
-        int qn = 0;
+        int qn = 0;   // guard-band entries: q[qcap - 1], q[qcap - 2], ...
+        int hn = 0;   // needed entries: q[0], q[1], ...
+        __shared__ int s_hn[NW];
+        constexpr uint32_t sal_bit = (METHOD == R360_DEPTH_CONSISTENCY) ? R360_PK_SAL_D : R360_PK_SAL_P;
+        const uint32_t nosal = J.nosal;
         const uint32_t* __restrict__ spk = J.spk;
         const auto rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(spk), 0, npx * 4, 0x00020000);
         const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(tg), 0, npx * 16, 0x00020000);
         const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(J.tpk), 0, npx * 4, 0x00020000);
-        auto gray_of = [](unsigned v) { return (float)(v >> 16) * (float)(1. / 255); };   // k_stitch4's expressions
+        // k_stitch4's expressions; the luma masked to its 8 bits (the saliency flags sit above it)
+        auto gray_of = [](unsigned v) { return (float)((v >> 16) & 0xffu) * (float)(1. / 255); };
         auto depth_of = [](unsigned v) { return (float)(v & 0xffffu) * 0.001f; };
         auto gG = [&](int t) {
             const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs_g, t * 16, 0, 0);
@@ -902,8 +932,21 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
             if (m) {
                 const int pos = qn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
                                                                    __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                if (o.fix) { q[pos] = base + lane; o.vis = false; o.t = 0; }
+                if (o.fix) { q[qcap - 1 - pos] = base + lane; o.vis = false; o.t = 0; }
                 qn += __popcll(m);
+            }
+        };
+        // a chunk whose target words have arrived: its visible lanes that are not needed are counted here (the
+        // needed ones by contribute_lean in the heavy stage), the needed ones queued
+        auto sift = [&](bool vis, unsigned tv, int base) {
+            const bool need = vis && ((tv | nosal) & sal_bit) != 0;
+            W.c28 += wave_count(vis && !need);
+            const unsigned long long m = __ballot(need);
+            if (m) {
+                const int pos = hn + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                if (need) q[pos] = base + lane;
+                hn += __popcll(m);
             }
         };
         const int nbx = (int)gridDim.x;   // XCD-aware stream order (as PF 5)
@@ -916,45 +959,94 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
             cur_r = __builtin_amdgcn_readfirstlane(row_of(b0));
             cur_c = b0 - cur_r * nCols;
             auto base = [&](int k) { return b0 + (k < n_it ? k : n_it - 1) * stride; };
+            // three register roles (A, B, C): while chunk k is sifted, the target words of chunks k + 1 and k + 2 and
+            // the source words of the three chunks after them are in flight
             Src sA = ld();
             Src sB = ld();
+            Src sC = ld();
             Proj oA = prj(sA);
             defer(oA, base(0));
-            float4 GA = gG(oA.t);
             unsigned TA = gT(oA.t);
-            for (int k = 0;; k += 2) {
-                sA = ld();
-                Proj oB = prj(sB);
-                if (k + 1 < n_it) defer(oB, base(k + 1));   // a clamped tail chunk is never accumulated
-                const float4 GB = gG(oB.t);
-                const unsigned TB = gT(oB.t);
-                acc(oA, GA, TA);
+            sA = ld();
+            Proj oB = prj(sB);
+            if (1 < n_it) defer(oB, base(1));   // a clamped tail chunk is never sifted
+            unsigned TB = gT(oB.t);
+            sB = ld();
+            for (int k = 0;; k += 3) {
+                Proj oC = prj(sC);
+                if (k + 2 < n_it) defer(oC, base(k + 2));
+                const unsigned TC = gT(oC.t);
+                sC = ld();
+                sift(oA.vis, TA, base(k));
                 if (k + 1 >= n_it) break;
-                sB = ld();
                 oA = prj(sA);
-                if (k + 2 < n_it) defer(oA, base(k + 2));
-                GA = gG(oA.t);
+                if (k + 3 < n_it) defer(oA, base(k + 3));
                 TA = gT(oA.t);
-                acc(oB, GB, TB);
+                sA = ld();
+                sift(oB.vis, TB, base(k + 1));
                 if (k + 2 >= n_it) break;
+                oB = prj(sB);
+                if (k + 4 < n_it) defer(oB, base(k + 4));
+                TB = gT(oB.t);
+                sB = ld();
+                sift(oC.vis, TC, base(k + 2));
+                if (k + 3 >= n_it) break;
             }
         }
-        // the workgroup's deferred lanes, drained together (as PF 5)
-        if (lane == 0) s_qn[tidx >> 6] = qn;
+        // the workgroup's queues as two lists (as PF 5's drain: wave w's entries after those of waves < w, 64 entries
+        // per chunk, chunk j on wave j % NW); the barrier orders the other waves' queue stores before the loads
+        if (lane == 0) { s_qn[tidx >> 6] = qn; s_hn[tidx >> 6] = hn; }
         __syncthreads();
-        int pre[NW + 1];
+        int pre[NW + 1], hpre[NW + 1];
         pre[0] = 0;
+        hpre[0] = 0;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) pre[w + 1] = pre[w] + s_qn[w];
-        const int tot = pre[NW];
+        for (int w = 0; w < NW; ++w) { pre[w + 1] = pre[w] + s_qn[w]; hpre[w + 1] = hpre[w] + s_hn[w]; }
+        const int tot = pre[NW], htot = hpre[NW];
         const int* qb = dq + (long)bidx * NW * qcap;
+        // the heavy stage.  The next chunk's entries, source words and tables are loaded before this chunk's
+        // projection, so that two of the three dependent memory round trips of a chunk overlap the previous one's work
+        struct HSrc { unsigned v; float sp, cp, st, ct; bool act; };
+        const auto rs_sp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(sinphi), 0, nRows * 4, 0x00020000);
+        const auto rs_cp = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cosphi), 0, nRows * 4, 0x00020000);
+        auto hld = [&](int s0) {
+            const int g = s0 + lane;
+            const bool act = g < htot;
+            int w = 0;
+#pragma unroll
+            for (int v = 1; v < NW; ++v) w += g >= hpre[v] ? 1 : 0;
+            const int i = act ? qb[w * qcap + (g - hpre[w])] : 0;
+            // row_of: the float estimate is off by at most one row for any 31-bit pixel index, and the two integer
+            // corrections settle it
+            const int r = row_of(i), c = i - r * nCols;
+            return HSrc{__builtin_amdgcn_raw_buffer_load_b32(rs_s, i * 4, 0, 0),
+                        __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_sp, r * 4, 0, 0)),
+                        __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_cp, r * 4, 0, 0)),
+                        __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_st, c * 4, 0, 0)),
+                        __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_ct, c * 4, 0, 0)), act};
+        };
+        {
+            int s0 = (tidx >> 6) * 64;
+            HSrc hA = hld(s0);
+            while (s0 < htot) {
+                const HSrc hB = hld(s0 + NW * 64);   // past the list: inactive lanes reading pixel 0
+                Proj o = project_fast<true>(P, lut_point(depth_of(hA.v), hA.sp, hA.cp, hA.st, hA.ct, C), gray_of(hA.v),
+                                            nRows, nCols, angle_res_inv, asin_out);
+                o.vis = o.vis && hA.act;
+                o.t = o.vis ? o.t : 0;
+                acc(o, gG(o.t), gT(o.t));
+                hA = hB;
+                s0 += NW * 64;
+            }
+        }
+        // the workgroup's guard-band lanes, drained together (as PF 5)
         for (int s0 = (tidx >> 6) * 64; s0 < tot; s0 += NW * 64) {
             const int g = s0 + lane;
             const bool act = g < tot;
             int w = 0;
 #pragma unroll
             for (int v = 1; v < NW; ++v) w += g >= pre[v] ? 1 : 0;
-            const int i = act ? qb[w * qcap + (g - pre[w])] : 0;
+            const int i = act ? qb[w * qcap + (qcap - 1 - (g - pre[w]))] : 0;
             const unsigned v = spk[i];
             const int r = i / nCols, c = i - r * nCols;
             Proj o = project_exact(P, lut_point(depth_of(v), sinphi[r], cosphi[r], sinth[c], costh[c], C), gray_of(v),
@@ -1925,6 +2017,14 @@ static PassGrid pass_grid(const r360_ctx* ctx, const LevelBufs& Ls, int occ, int
     return {pf, nb};
 }
 
+// The target's saliency flags serve an alignment whose thresholds are at least those the flags were built for: they
+// then mark a superset of the pixels contribute_lean accepts, and its own tests decide.  Otherwise (lower thresholds,
+// or a frame without flags: NaN compares false) the pass treats every pixel as flagged: correct, and slower than the
+// dense form was, since every visible pixel then goes through the queue.
+uint32_t icp_pk_nosal(const r360_frame* trg, float thr_int, float thr_depth) {
+    return (trg->sal_int <= thr_int && trg->sal_depth <= thr_depth) ? 0u : R360_PK_SAL;
+}
+
 int icp_pass_form(const r360_ctx* ctx, const r360_frame* src, int level, int occ, bool batched) {
     return pass_grid(ctx, src->lv[level], occ, 1, batched, !batched && ((src->compacted >> level) & 1u)).pf;
 }
@@ -2030,7 +2130,7 @@ int launch_icp_level_persist(r360_ctx* ctx, const r360_frame* trg, const r360_fr
     IcpJobs jobs;
     IcpJob& J = jobs.j[0];
     J.src = Ls.p0; J.trg = Lt.p0; J.tg = Lt.tg; J.pts = Ls.pts; J.npts = src->d_npts + level;
-    J.spk = Ls.pk; J.tpk = Lt.pk;
+    J.spk = Ls.pk; J.tpk = Lt.pk; J.nosal = icp_pk_nosal(trg, C0.thr_int, C0.thr_depth); J.pad = 0;
     J.S = ctx->d_state; J.partials = ctx->d_partials; J.gcnt = ctx->d_gticket; J.dq = ctx->d_defer;
     IcpConst C = C0;
     if (++ctx->icp_seq == 0) ++ctx->icp_seq;
@@ -2106,7 +2206,7 @@ int launch_icp_level(r360_ctx* ctx, const r360_frame* trg, const r360_frame* src
     IcpJobs jobs;
     IcpJob& J = jobs.j[0];
     J.src = Ls.p0; J.trg = Lt.p0; J.tg = Lt.tg; J.pts = Ls.pts; J.npts = src->d_npts + level;
-    J.spk = Ls.pk; J.tpk = Lt.pk;
+    J.spk = Ls.pk; J.tpk = Lt.pk; J.nosal = icp_pk_nosal(trg, C.thr_int, C.thr_depth); J.pad = 0;
     J.S = ctx->d_state; J.partials = ctx->d_partials; J.gcnt = ctx->d_gticket; J.dq = ctx->d_defer;
     return launch_jobs(ctx, jobs, 1, Ls, T, level, method, C, first, eval_only, G);
 }

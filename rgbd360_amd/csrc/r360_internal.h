@@ -73,8 +73,14 @@ struct LevelBufs {
     // level 0 only: the level's {gray, depth} as the stitch produced them, 4 B per pixel: range in mm (u16) |
     // luma (u8) << 16.  gray = luma * (float)(1/255), depth = range * 0.001f reproduce p0 bit for bit; the
     // level-0 ICP pass (PF 6) streams the source and gathers the target {gray, depth} from these.
+    // Bits 24 / 25 (R360_PK_SAL_P / _D) are the pixel's saliency flags, set by the pyramid build (k_prep_l0) from the
+    // level-0 gradients it stores in tg: every reader of the word masks the luma to 8 bits.
     uint32_t* pk = nullptr;
 };
+// saliency flags of a packed level-0 word: the pixel's intensity / depth gradient passes the threshold the flags were
+// built for (contribute_lean's sal_p / sal_d tests; r360_frame::sal_int / sal_depth)
+constexpr uint32_t R360_PK_SAL_P = 1u << 24, R360_PK_SAL_D = 1u << 25, R360_PK_SAL = R360_PK_SAL_P | R360_PK_SAL_D;
+constexpr uint32_t R360_PK_VALUE = 0x00ffffffu;   // range mm | luma << 16
 constexpr int R360_SRC_BLOCK = 4096;   // pixels per block of the source-point compaction
 // one level's inputs / output of the compaction (a device-side table per frame, fixed at creation)
 struct SrcLevel { const float2* p0; float4* pts; const float* sinphi; const float* cosphi; const float* sinth;
@@ -144,12 +150,17 @@ struct IcpJob {
     const int* npts;            // their count
     const uint32_t* spk;        // level 0: source packed {range mm, luma} image (PF 6)
     const uint32_t* tpk;        // level 0: target packed image
+    // PF 6: OR-ed into the gathered target word before its saliency flags are read.  0 where the target's flags were
+    // built for thresholds <= the alignment's (they then mark a superset of its salient pixels); R360_PK_SAL where
+    // they were not, or the frame has none: every visible pixel then takes the heavy stage (icp_pk_nosal)
+    uint32_t nosal;
+    uint32_t pad;
     IcpState* S;
     double* partials;           // per-workgroup records
     unsigned* gcnt;             // group arrival counters (16384 words)
     int* dq;                    // deferred-pixel queues
 };
-struct IcpJobs { IcpJob j[R360_MAX_BATCH]; };   // passed by value (kernel arguments, 1152 B)
+struct IcpJobs { IcpJob j[R360_MAX_BATCH]; };   // passed by value (kernel arguments, 1280 B)
 
 constexpr int R360_KT_SLOTS = 26;
 // arrival tickets: a pass's workgroups count in 16 group counters, and each group's last workgroup sums its group's records
@@ -701,6 +712,9 @@ struct r360_frame {
     bool want_local = false;           // the next plane assembly keeps them (set by the build, taken by planes_spawn_assembly)
     uint64_t timestamp = 0;            // Frame360::timeStamp (Frame360.h:181-184)
     unsigned compacted = 0;            // bit l: lv[l].pts / d_npts[l] hold level l's compacted source points
+    // the thresholds lv[0].pk's saliency flags were built for (launch_pyramid: the r360_icp_default_params values);
+    // NaN: the words carry no flags (every writer of the whole word, the stitch and launch_sphere_level0, sets that)
+    float sal_int = __builtin_nanf(""), sal_depth = __builtin_nanf("");
     // the pyramid build compacts every level: a lone alignment's passes (PF 5) read the compacted points.  Frames that
     // only enter batched alignments (compact_all unset: the sequence runner's queued ring) skip it on every level a
     // batched pass streams as an image (PF 6 at level 0, PF 8 above; round 6: two launches per frame fewer), and
@@ -718,7 +732,10 @@ struct r360_frame {
 hipStream_t capture_stream(r360_ctx* ctx);   // ctx->cap_stream, created on first use (nullptr on failure)
 int launch_undistort(r360_frame* f);
 // lean: only lv[0].pk is stored (frame_level0_lean: the frame's other level-0 outputs have no reader yet)
-int launch_stitch(r360_frame* f, bool lean = false);
+// keep_pk: lv[0].pk is left as it is (frame_level0_materialise: the same values, and the pyramid's saliency flags)
+int launch_stitch(r360_frame* f, bool lean = false, bool keep_pk = false);
+// IcpJob::nosal of a level-0 pass against trg with the alignment's saliency thresholds
+uint32_t icp_pk_nosal(const r360_frame* trg, float thr_int, float thr_depth);
 bool frame_level0_lean(const r360_frame* f);
 // The full level-0 outputs (d_sph_bgr, d_sph_depth, lv[0].p0) of a frame whose last build was lean: the full stitch
 // again on the frame's stream, from the raw images still resident (an upload clears `built`), waited for, and
