@@ -19,7 +19,15 @@
 // :443, :613-628), Partitioner() runs when the keyframe's index in its area is a multiple of 4 (:710-717) and the
 // "Places" lines follow (:733-740); at the end a line per area gives its keyframes and its representative.  Without
 // the flag nothing of this runs or prints.
+// The reference optimises with every loop edge at full quadratic weight; three flags go beyond it:
+// --robust huber:D | cauchy:D gives the loop edges a robust kernel (the chain and PbMap edges stay quadratic),
+// --reject-chi2 T deactivates after each optimisation the loop edges whose chi2 exceeds T and optimises again, and
+// --false-loop I,J adds, with keyframe J, a loop edge I -> J whose measurement is the keyframes' current relative pose
+// composed with a fixed wrong transform (0.4 rad about y, (1.0, -0.7, 0.5) m) at J's dense Hessian.  With any of them
+// every optimisation is followed by a "loop edge I J chi2 X weight W" line per loop edge; without them the output is
+// what it was.
 //   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]
+//                       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J]
 //          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
 //          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
 #include <rgbd360/rgbd360.h>
@@ -56,9 +64,28 @@ int main(int argc, char** argv) {
     std::string save, frames_arg;
     int n_synth = 0;
     bool synthetic = false, submaps = false;
+    int robust_kind = R360_GRAPH_KERNEL_NONE;            // --robust: the loop edges' kernel
+    double robust_delta = 1.0;
+    double reject_chi2 = -1.0;                           // --reject-chi2: < 0 = off
+    int false_from = -1, false_to = -1;                  // --false-loop
+    bool bad_arg = false;
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
-        if (a == "--min-gap" && k + 1 < argc) min_gap = std::atoi(argv[++k]);
+        if (a == "--robust" && k + 1 < argc) {
+            const std::string v = argv[++k];
+            const size_t colon = v.find(':');
+            const std::string name = v.substr(0, colon);
+            robust_kind = name == "huber" ? R360_GRAPH_KERNEL_HUBER : name == "cauchy" ? R360_GRAPH_KERNEL_CAUCHY : -1;
+            robust_delta = colon == std::string::npos ? 0.0 : std::atof(v.c_str() + colon + 1);
+            bad_arg = bad_arg || robust_kind < 0 || !(robust_delta > 0.0);
+        } else if (a == "--reject-chi2" && k + 1 < argc) {
+            reject_chi2 = std::atof(argv[++k]);
+            bad_arg = bad_arg || !(reject_chi2 >= 0.0);
+        } else if (a == "--false-loop" && k + 1 < argc) {
+            bad_arg = bad_arg || std::sscanf(argv[++k], "%d,%d", &false_from, &false_to) != 2 || false_from < 0 ||
+                      false_to <= false_from;
+        }
+        else if (a == "--min-gap" && k + 1 < argc) min_gap = std::atoi(argv[++k]);
         else if (a == "--kf-dist" && k + 1 < argc) kf_dist = float(std::atof(argv[++k]));
         else if (a == "--save" && k + 1 < argc) save = argv[++k];
         else if (a == "--submaps") submaps = true;
@@ -74,11 +101,19 @@ int main(int argc, char** argv) {
         p = q + 1;
     }
     for (int k = 0; k < n_synth && frames_arg.empty(); ++k) order.push_back(k);
-    if ((synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
+    if (bad_arg || (synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
         std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
-                             "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n", argv[0]);
+                             "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n"
+                             "       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J]\n"
+                             "  --robust       loop edges get the kernel, of width D on sqrt(chi2); chain and PbMap edges stay quadratic\n"
+                             "  --reject-chi2  after each optimisation loop edges with chi2 > T are deactivated and the graph is optimised again\n"
+                             "  --false-loop   when keyframe J is added, also add a wrong loop edge I -> J (demonstration)\n"
+                             "  With any of the three, 'loop edge I J chi2 X weight W' is printed per loop edge after every optimisation\n"
+                             "  (--reject-chi2 inf prints and rejects nothing).  The dense Hessians are not calibrated information\n"
+                             "  matrices, so chi2 has no unit scale: choose D and T from these printed values.\n", argv[0]);
         return 1;
     }
+    const bool edge_report = robust_kind != R360_GRAPH_KERNEL_NONE || reject_chi2 >= 0.0 || false_from >= 0;
     const std::string dir = synthetic ? "" : pos[0];
     const int first = synthetic ? 0 : std::atoi(pos[1].c_str()), step = synthetic ? 1 : std::atoi(pos[2].c_str());
     const size_t occ_at = synthetic ? 0 : 3;
@@ -156,6 +191,32 @@ int main(int argc, char** argv) {
         Matrix4f rigidTransf_dense_ref = Matrix4f::Identity();
         int loops = 0, optimisations = 0;
         double F_first = 0.0, F_last = 0.0;
+        // the loop edges by their index in the graph: the ones that may carry a kernel and may be rejected
+        struct LoopEdge { int edge, from, to; bool active; double chi2; };
+        std::vector<LoopEdge> loopEdges;
+        auto addLoopEdge = [&](int from, int to, const Matrix4f& rel, const r360::Matrix6f& info) {
+            const int edge = optimizer.numEdges();
+            optimizer.addEdge(from, to, rel.cast<double>(), info.cast<double>());
+            if (robust_kind != R360_GRAPH_KERNEL_NONE) optimizer.setEdgeRobustKernel(edge, robust_kind, robust_delta);
+            loopEdges.push_back(LoopEdge{edge, from, to, true, 0.0});
+        };
+        auto optimise = [&]() {                          // :679-705
+            optimizer.optimizeGraph();
+            optimizer.getPoses(vOptimizedPoses);
+            currentPose = vOptimizedPoses.back();
+            const r360_graph_stats& st = optimizer.stats();
+            if (optimisations++ == 0) F_first = st.F_initial;
+            F_last = st.F_final;
+            std::printf("Optimize graph SLAM %zu: status %d iterations %d cost %.9g -> %.9g\n", kfs.size(), st.status, st.iterations,
+                        st.F_initial, st.F_final);
+            if (!edge_report) return;
+            std::vector<double> chi2, weight;
+            optimizer.getEdgeChi2(chi2, &weight);
+            for (LoopEdge& le : loopEdges) {
+                le.chi2 = chi2[le.edge];
+                std::printf("loop edge %d %d chi2 %.9g weight %.9g\n", le.from, le.to, le.chi2, weight[le.edge]);
+            }
+        };
         for (size_t n = 1;; ++n) {
             std::unique_ptr<r360::Frame360> frame(new r360::Frame360(&calib));
             if (!load(*frame, n, &id)) break;
@@ -229,22 +290,37 @@ int main(int argc, char** argv) {
                 relativePose = rotOffsetInv * align360.getOptimalPose() * rotOffset;
                 const r360::Matrix6f informationMatrix = align360.getHessian();
                 if (lok && (!occlusion || align360.avDepthResidual < 2.0)) {
-                    optimizer.addEdge(compareLocalIdx, newFrameID, relativePose.cast<double>(), informationMatrix.cast<double>());
+                    addLoopEdge(compareLocalIdx, newFrameID, relativePose, informationMatrix);
                     std::printf("LC Add edge between %d and %d (residual %.5f)\n", compareLocalIdx, newFrameID, align360.avDepthResidual);
                     if (submaps) topologicalMap->addConnection(unsigned(newFrameID), unsigned(compareLocalIdx), align360.SSO);   // :628
                     bHasNewLC = true;
                     ++loops;
                 }
             }
+            if (newFrameID == false_to && false_from < newFrameID) {   // --false-loop: a wrong pair that passed the matcher
+                Matrix4f wrong = Matrix4f::Identity();   // 0.4 rad about y, then (1.0, -0.7, 0.5) m
+                wrong(0, 0) = wrong(2, 2) = std::cos(0.4f);
+                wrong(0, 2) = std::sin(0.4f);
+                wrong(2, 0) = -wrong(0, 2);
+                wrong(0, 3) = 1.0f; wrong(1, 3) = -0.7f; wrong(2, 3) = 0.5f;
+                const Matrix4f relativePose = vOptimizedPoses[false_from].inverse() * currentPose * wrong;
+                addLoopEdge(false_from, newFrameID, relativePose, hessian);
+                std::printf("LC Add false edge between %d and %d\n", false_from, newFrameID);
+                bHasNewLC = true;
+                ++loops;
+            }
             if (bHasNewLC) {                             // :679-705
-                optimizer.optimizeGraph();
-                optimizer.getPoses(vOptimizedPoses);
-                currentPose = vOptimizedPoses.back();
-                const r360_graph_stats& st = optimizer.stats();
-                if (optimisations++ == 0) F_first = st.F_initial;
-                F_last = st.F_final;
-                std::printf("Optimize graph SLAM %zu: status %d iterations %d cost %.9g -> %.9g\n", kfs.size(), st.status, st.iterations,
-                            st.F_initial, st.F_final);
+                optimise();
+                bool rejected = false;
+                if (reject_chi2 >= 0.0)
+                    for (LoopEdge& le : loopEdges)
+                        if (le.active && le.chi2 > reject_chi2) {
+                            optimizer.setEdgeActive(le.edge, false);
+                            le.active = false;
+                            rejected = true;
+                            std::printf("LC reject edge between %d and %d chi2 %.9g\n", le.from, le.to, le.chi2);
+                        }
+                if (rejected) optimise();
             }
             if (submaps && newLocalFrameID % 4 == 0) {   // Visibility division (Normalized-cut), :710-740
                 topologicalMap->Partitioner();

@@ -925,6 +925,32 @@ class GraphOptimizer {
     void addEdge(const int fromIdx, const int toIdx, const Matrix4d relativePose, const Matrix6d informationMatrix) {
         check(r360_graph_add_edge(h_, fromIdx, toIdx, relativePose.data(), informationMatrix.data()), "GraphOptimizer::addEdge");
     }
+    // g2o's setRobustKernel, per edge (kind: R360_GRAPH_KERNEL_NONE / _HUBER / _CAUCHY, delta on sqrt(chi2)): the
+    // first call sets the kernel of the edges added from now on, the second that of one edge.  Edges are numbered
+    // in the order of the addEdge calls.
+    void setRobustKernel(int kind, double delta = 1.0) {
+        check(r360_graph_set_default_kernel(h_, kind, delta), "GraphOptimizer::setRobustKernel");
+    }
+    void setEdgeRobustKernel(int edge, int kind, double delta = 1.0) {
+        check(r360_graph_set_edge_kernel(h_, edge, kind, delta), "GraphOptimizer::setEdgeRobustKernel");
+    }
+    // an inactive edge does not exist for optimizeGraph and saveGraph
+    void setEdgeActive(int edge, bool active) {
+        check(r360_graph_set_edge_active(h_, edge, active ? 1 : 0), "GraphOptimizer::setEdgeActive");
+    }
+    // per edge at the current poses: chi2 = e^T info e and the kernel's weight (0 for an inactive edge)
+    void getEdgeChi2(std::vector<double>& chi2, std::vector<double>* weight = nullptr) {
+        const int m = numEdges();
+        int n = 0;
+        chi2.assign(size_t(m), 0.0);
+        if (weight) weight->assign(size_t(m), 0.0);
+        check(r360_graph_edge_stats(h_, chi2.data(), weight ? weight->data() : nullptr, m, &n), "GraphOptimizer::getEdgeChi2");
+    }
+    int numEdges() const {
+        int m = 0;
+        check(r360_graph_size(h_, nullptr, &m), "GraphOptimizer::numEdges");
+        return m;
+    }
     void optimizeGraph() { check(r360_graph_optimize(h_, &params, &stats_), "GraphOptimizer::optimizeGraph"); }
     template <class Alloc>
     void getPoses(std::vector<Matrix4f, Alloc>& poses) {

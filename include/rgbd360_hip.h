@@ -806,6 +806,31 @@ int  r360_graph_set_pose(r360_graph* g, int id, const double pose[16]);
  * LoopClosure360.h:318).  Either index order; several edges of one pair add up. */
 int  r360_graph_add_edge(r360_graph* g, int from, int to, const double rel[16], const double info[36]);
 int  r360_graph_size(const r360_graph* g, int* n_vertices, int* n_edges);
+/* Robust kernels and the active set (g2o's setRobustKernel, per edge).  Edges are numbered in
+ * insertion order, 0 .. n_edges - 1 of r360_graph_size.  With c = e^T info e of an edge and its width delta > 0
+ * (delta applies to sqrt(c), as in g2o's RobustKernelHuber / RobustKernelCauchy):
+ *   R360_GRAPH_KERNEL_NONE    rho(c) = c                                   w = 1
+ *   R360_GRAPH_KERNEL_HUBER   rho(c) = c for c <= delta^2, otherwise
+ *                                      2 delta sqrt(c) - delta^2           w = delta / sqrt(c)
+ *   R360_GRAPH_KERNEL_CAUCHY  rho(c) = delta^2 log1p(c / delta^2)          w = 1 / (1 + c / delta^2)
+ * The cost is F = sum rho(c); an edge adds w J^T info e to b and J^T (w info) J to H (the second-order term is left
+ * out, as g2o leaves it out); Levenberg-Marquardt is unchanged, with the robust F in its gain ratio.  A graph whose
+ * edges all have NONE computes bit for bit what it computed before kernels existed.
+ * An inactive edge does not exist for eval, solve and optimize: it adds nothing, the graph checks do not count it (a
+ * free vertex whose only edges are inactive is R360_EINVAL, as is a component anchored only through inactive edges),
+ * and a graph with edge k inactive gives the same bytes as the same graph built without edge k.
+ * set_default_kernel: the kernel of the edges added (or loaded) from now on; NONE at creation.  R360_EINVAL on an
+ * unknown kind, a delta that is not finite and positive (whatever the kind) or a bad edge index; nothing changes then. */
+enum { R360_GRAPH_KERNEL_NONE = 0, R360_GRAPH_KERNEL_HUBER = 1, R360_GRAPH_KERNEL_CAUCHY = 2 };
+int  r360_graph_set_default_kernel(r360_graph* g, int kind, double delta);
+int  r360_graph_set_edge_kernel(r360_graph* g, int edge, int kind, double delta);
+int  r360_graph_get_edge_kernel(const r360_graph* g, int edge, int* kind, double* delta);
+int  r360_graph_set_edge_active(r360_graph* g, int edge, int active);
+int  r360_graph_get_edge_active(const r360_graph* g, int edge, int* active);
+/* Per edge at the current poses: chi2 [cap] = c and weight [cap] = w of the edge's kernel, computed on the GPU by the
+ * cost-only form of the linearisation.  An inactive edge reports its chi2 with weight 0.  Either output may be NULL;
+ * *n = n_edges is set either way; cap < *n with an output given is an error. */
+int  r360_graph_edge_stats(r360_graph* g, double* chi2, double* weight, int cap, int* n);
 /* getPoses (GraphOptimizer.h:160-175): poses [cap][16]; *n is set either way, cap < *n with poses given is an error. */
 int  r360_graph_get_poses(const r360_graph* g, double* poses, int cap, int* n);
 void r360_graph_default_params(r360_graph_params* p);
@@ -832,7 +857,9 @@ int  r360_g2o_write(const char* path, int n_vertices, const double* poses, const
                     const double* rel, const double* info);
 int  r360_g2o_read(const char* path, double* poses, int* fixed, int cap_vertices, int* n_vertices, int* ij, double* rel,
                    double* info, int cap_edges, int* n_edges);
-/* saveGraph / the matching load: load replaces the graph's vertices and edges. */
+/* saveGraph / the matching load: load replaces the graph's vertices and edges.  save writes the active edges only:
+ * the file is the graph that gets optimised.  g2o text has no place for robust kernels, so none is written; load
+ * gives every edge it reads the current default kernel and makes it active. */
 int  r360_graph_save(const r360_graph* g, const char* path);
 int  r360_graph_load(r360_graph* g, const char* path);
 

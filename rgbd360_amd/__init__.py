@@ -108,6 +108,7 @@ class GraphStats(C.Structure):
 
 
 GRAPH_CONVERGED, GRAPH_ITERATION_LIMIT, GRAPH_STALLED, GRAPH_CG_NOT_CONVERGED = 0, 1, 2, 3
+GRAPH_KERNEL_NONE, GRAPH_KERNEL_HUBER, GRAPH_KERNEL_CAUCHY = 0, 1, 2   # R360_GRAPH_KERNEL_*
 
 
 class TopoParams(C.Structure):
@@ -437,6 +438,12 @@ _SIGS = [
     ("r360_graph_set_pose", C.c_int, [_P, C.c_int, _DP]),
     ("r360_graph_add_edge", C.c_int, [_P, C.c_int, C.c_int, _DP, _DP]),
     ("r360_graph_size", C.c_int, [_P, _IP, _IP]),
+    ("r360_graph_set_default_kernel", C.c_int, [_P, C.c_int, C.c_double]),
+    ("r360_graph_set_edge_kernel", C.c_int, [_P, C.c_int, C.c_int, C.c_double]),
+    ("r360_graph_get_edge_kernel", C.c_int, [_P, C.c_int, _IP, _DP]),
+    ("r360_graph_set_edge_active", C.c_int, [_P, C.c_int, C.c_int]),
+    ("r360_graph_get_edge_active", C.c_int, [_P, C.c_int, _IP]),
+    ("r360_graph_edge_stats", C.c_int, [_P, _DP, _DP, C.c_int, _IP]),
     ("r360_graph_get_poses", C.c_int, [_P, _DP, C.c_int, _IP]),
     ("r360_graph_default_params", None, [C.POINTER(GraphParams)]),
     ("r360_graph_optimize", C.c_int, [_P, C.POINTER(GraphParams), C.POINTER(GraphStats)]),
@@ -1874,6 +1881,38 @@ class PoseGraph:
         nv, ne = C.c_int(), C.c_int()
         _check(lib().r360_graph_size(self.h, C.byref(nv), C.byref(ne)), "graph_size")
         return nv.value, ne.value
+
+    def numEdges(self) -> int:
+        return self.size()[1]
+
+    def setRobustKernel(self, kind: int, delta: float = 1.0):
+        """The kernel (GRAPH_KERNEL_*) of the edges added from now on; delta applies to sqrt(chi2)."""
+        _check(lib().r360_graph_set_default_kernel(self.h, kind, delta), "graph_set_default_kernel")
+
+    def setEdgeRobustKernel(self, edge: int, kind: int, delta: float = 1.0):
+        _check(lib().r360_graph_set_edge_kernel(self.h, edge, kind, delta), "graph_set_edge_kernel")
+
+    def getEdgeRobustKernel(self, edge: int):
+        kind, delta = C.c_int(), C.c_double()
+        _check(lib().r360_graph_get_edge_kernel(self.h, edge, C.byref(kind), C.byref(delta)), "graph_get_edge_kernel")
+        return kind.value, delta.value
+
+    def setEdgeActive(self, edge: int, active: bool = True):
+        """An inactive edge does not exist for eval, solve, optimizeGraph and saveGraph."""
+        _check(lib().r360_graph_set_edge_active(self.h, edge, int(active)), "graph_set_edge_active")
+
+    def getEdgeActive(self, edge: int) -> bool:
+        a = C.c_int()
+        _check(lib().r360_graph_get_edge_active(self.h, edge, C.byref(a)), "graph_get_edge_active")
+        return bool(a.value)
+
+    def getEdgeChi2(self):
+        """r360_graph_edge_stats: (chi2 [n_edges], weight [n_edges]) at the current poses; an inactive edge has weight 0."""
+        m = self.numEdges()
+        chi2, w = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        n = C.c_int()
+        _check(lib().r360_graph_edge_stats(self.h, _dptr(chi2), _dptr(w), m, C.byref(n)), "graph_edge_stats")
+        return chi2[:m].copy(), w[:m].copy()
 
     def getPoses(self) -> np.ndarray:
         n = self.size()[0]

@@ -2,7 +2,9 @@
 // kernels/pgo_kernels.hip; statement and design: tests/pgo_model.py, DESIGN.md §5d.  The graph lives on the host; an
 // optimise call checks it, builds the block structure (the distinct block columns per free vertex, the by-vertex list
 // of (edge, side) entries in edge order), uploads everything and runs Levenberg-Marquardt: the damping, accept /
-// reject and stop decisions here, from one small read-back per trial, everything else on the device.
+// reject and stop decisions here, from one small read-back per trial, everything else on the device.  Every edge has
+// a robust kernel and an active flag; the device sees the active edges alone, renumbered in edge order, so an
+// inactive edge leaves no trace in any sum.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,11 +21,16 @@ struct r360_graph {
     std::vector<int> ij;          // [m][2]
     std::vector<double> Z;        // [m][16] column-major
     std::vector<double> Om;       // [m][36] symmetrised
+    std::vector<int> kind;        // [m] R360_GRAPH_KERNEL_*
+    std::vector<double> kdelta;   // [m] the kernel's width (never read where the kind is NONE)
+    std::vector<char> active;     // [m]
+    int def_kind = R360_GRAPH_KERNEL_NONE;   // what add_edge and load give an edge
+    double def_delta = 1.0;
     // device: the handle owns the buffers (host/devmem.h); D is the view of them the kernels take, refilled by prepare
     struct {
         DevBuf<int2> ij;
-        DevBuf<int> vfree, fidx, vptr, ventry, vblk, rowptr, colidx, diag;
-        DevBuf<double> Z, Om, Hs, bs, lin, cost, vals, b, minv;
+        DevBuf<int> kind, vfree, fidx, vptr, ventry, vblk, rowptr, colidx, diag;
+        DevBuf<double> Z, Om, kdelta, Hs, bs, lin, cost, chi2, wgt, vals, b, minv;
     } own;
     PgoDev D;
     DevBuf<double> pose[2];                 // [n][12] row-major 3x4: the current and the trial poses
@@ -56,10 +63,19 @@ struct Structure {
     std::vector<int> fidx, vfree, vptr, ventry, vblk, rowptr, colidx, diag;
 };
 
+// the active edges, in edge order
+std::vector<int> active_edges(const r360_graph* g) {
+    std::vector<int> sel;
+    for (int e = 0; e < (int)g->active.size(); ++e)
+        if (g->active[e]) sel.push_back(e);
+    return sel;
+}
+
 // the graph-level checks (a free vertex with no edge; a connected component with no fixed vertex: union-find over the
-// edges) and the block structure
-int build_structure(const r360_graph* g, Structure& S) {
-    const int n = (int)g->fixed.size(), m = (int)(g->ij.size() / 2);
+// edges) and the block structure, both over the edges sel alone, numbered by their place in sel
+int build_structure(const r360_graph* g, const std::vector<int>& sel, Structure& S) {
+    const int n = (int)g->fixed.size(), m = (int)sel.size();
+    auto end_of = [&](int e, int s) { return g->ij[2 * (size_t)sel[e] + s]; };
     std::vector<int> parent(n), deg(n, 0);
     std::iota(parent.begin(), parent.end(), 0);
     auto find = [&](int a) {
@@ -67,7 +83,7 @@ int build_structure(const r360_graph* g, Structure& S) {
         return a;
     };
     for (int e = 0; e < m; ++e) {
-        const int i = g->ij[2 * e], j = g->ij[2 * e + 1];
+        const int i = end_of(e, 0), j = end_of(e, 1);
         ++deg[i]; ++deg[j];
         parent[find(i)] = find(j);
     }
@@ -87,7 +103,7 @@ int build_structure(const r360_graph* g, Structure& S) {
     S.vptr.assign(nf + 1, 0);
     for (int e = 0; e < m; ++e)
         for (int s = 0; s < 2; ++s) {
-            const int k = S.fidx[g->ij[2 * e + s]];
+            const int k = S.fidx[end_of(e, s)];
             if (k >= 0) ++S.vptr[k + 1];
         }
     for (int k = 0; k < nf; ++k) S.vptr[k + 1] += S.vptr[k];
@@ -96,7 +112,7 @@ int build_structure(const r360_graph* g, Structure& S) {
     std::vector<int> at(S.vptr.begin(), S.vptr.end() - 1);
     for (int e = 0; e < m; ++e)
         for (int s = 0; s < 2; ++s) {
-            const int k = S.fidx[g->ij[2 * e + s]];
+            const int k = S.fidx[end_of(e, s)];
             if (k >= 0) S.ventry[at[k]++] = e * 2 + s;
         }
     // distinct block columns per row, ascending, the diagonal among them
@@ -108,7 +124,7 @@ int build_structure(const r360_graph* g, Structure& S) {
         cols.assign(1, k);
         for (int q = S.vptr[k]; q < S.vptr[k + 1]; ++q) {
             const int ent = S.ventry[q];
-            const int o = S.fidx[g->ij[2 * (ent >> 1) + (1 - (ent & 1))]];
+            const int o = S.fidx[end_of(ent >> 1, 1 - (ent & 1))];
             if (o >= 0) cols.push_back(o);
         }
         std::sort(cols.begin(), cols.end());
@@ -116,7 +132,7 @@ int build_structure(const r360_graph* g, Structure& S) {
         const int base = (int)S.colidx.size();
         for (int q = S.vptr[k]; q < S.vptr[k + 1]; ++q) {
             const int ent = S.ventry[q];
-            const int o = S.fidx[g->ij[2 * (ent >> 1) + (1 - (ent & 1))]];
+            const int o = S.fidx[end_of(ent >> 1, 1 - (ent & 1))];
             if (o >= 0) S.vblk[q] = base + (int)(std::lower_bound(cols.begin(), cols.end(), o) - cols.begin());
         }
         S.diag[k] = base + (int)(std::lower_bound(cols.begin(), cols.end(), k) - cols.begin());
@@ -133,13 +149,60 @@ int upload(hipStream_t st, T* dst, const std::vector<T>& src) {
     return 0;
 }
 
-// checks, structure, buffers, upload; the current poses land in g->pose[0].  The host vectors of this call live
-// until its ctx_wait.
+// the host copies of one upload of poses and edges; they live until the ctx_wait after it
+struct Staged {
+    std::vector<double> P, Z, Om, kdelta;
+    std::vector<int2> ij;
+    std::vector<int> kind;
+};
+
+// The current poses into g->pose[0] and the edges sel, in that order, with their kernels into the per-edge arrays
+// of g->D (D.n and D.m set): all that the cost-only linearisation reads.  No wait: the caller's is the one.
+int stage_edges(r360_graph* g, const std::vector<int>& sel, Staged& H) {
+    const int n = (int)g->fixed.size(), m = (int)sel.size();
+    r360_ctx* ctx = g->ctx;
+    auto& O = g->own;
+    const size_t mm = std::max(m, 1);
+    if (g->pose[0].reserve(ctx, 12 * (size_t)n) || O.ij.reserve(ctx, mm) || O.Z.reserve(ctx, 12 * mm) ||
+        O.Om.reserve(ctx, 36 * mm) || O.kind.reserve(ctx, mm) || O.kdelta.reserve(ctx, mm) || O.cost.reserve(ctx, mm) ||
+        O.chi2.reserve(ctx, mm) || O.wgt.reserve(ctx, mm) || g->partials.reserve(ctx, R360_PGO_MAXB))
+        return -1;
+    PgoDev& D = g->D;
+    D.n = n; D.m = m;
+    D.ij = O.ij.get(); D.Z = O.Z.get(); D.Om = O.Om.get(); D.kind = O.kind.get(); D.kdelta = O.kdelta.get();
+    D.cost = O.cost.get(); D.chi2 = O.chi2.get(); D.wgt = O.wgt.get();
+    H.P.resize(12 * (size_t)n);
+    H.Z.resize(12 * (size_t)m);
+    H.ij.resize(m);
+    H.kind.resize(m);
+    H.kdelta.resize(m);
+    const bool all = m == (int)g->active.size();   // then sel is 0 .. m - 1 and Omega goes up from where it lies
+    if (!all) H.Om.resize(36 * (size_t)m);
+    for (int v = 0; v < n; ++v) pose12(&g->poses[16 * (size_t)v], &H.P[12 * (size_t)v]);
+    for (int k = 0; k < m; ++k) {
+        const size_t e = (size_t)sel[k];
+        pose12(&g->Z[16 * e], &H.Z[12 * (size_t)k]);
+        H.ij[k] = make_int2(g->ij[2 * e], g->ij[2 * e + 1]);
+        H.kind[k] = g->kind[e];
+        H.kdelta[k] = g->kdelta[e];
+        if (!all) memcpy(&H.Om[36 * (size_t)k], &g->Om[36 * e], sizeof(double) * 36);
+    }
+    hipStream_t st = ctx->stream;
+    if (upload(st, g->pose[0].get(), H.P) || upload(st, D.Z, H.Z) || upload(st, D.ij, H.ij) ||
+        upload(st, D.Om, all ? g->Om : H.Om) || upload(st, D.kind, H.kind) || upload(st, D.kdelta, H.kdelta))
+        return -1;
+    return 0;
+}
+
+// checks, structure, buffers, upload, all over the active edges; the current poses land in g->pose[0].  The host
+// vectors of this call live until its ctx_wait.
 int prepare(r360_graph* g) {
-    const int n = (int)g->fixed.size(), m = (int)(g->ij.size() / 2);
+    const int n = (int)g->fixed.size();
     CHECK_ARG(n >= 1, "graph: no vertex");
+    const std::vector<int> sel = active_edges(g);
+    const int m = (int)sel.size();
     Structure S;
-    if (int rc = build_structure(g, S)) return rc;
+    if (int rc = build_structure(g, sel, S)) return rc;
     r360_ctx* ctx = g->ctx;
     if (bind_device(ctx->device)) return -1;
     const int nf = (int)S.vfree.size(), nnzb = (int)S.colidx.size();
@@ -147,31 +210,24 @@ int prepare(r360_graph* g) {
     auto& O = g->own;
     const size_t mm = std::max(m, 1), f = std::max(nf, 1), e1 = std::max<size_t>(ent, 1), nz = std::max(nnzb, 1);
     const size_t npart = std::max<size_t>(R360_PGO_MAXB, 3 * (size_t)((6 * nf + R360_PGO_CGM_TPB - 1) / R360_PGO_CGM_TPB));
-    if (g->pose[0].reserve(ctx, 12 * (size_t)n) || g->pose[1].reserve(ctx, 12 * (size_t)n) || O.fidx.reserve(ctx, n) ||
-        O.ij.reserve(ctx, mm) || O.Z.reserve(ctx, 12 * mm) || O.Om.reserve(ctx, 36 * mm) ||
+    if (g->pose[1].reserve(ctx, 12 * (size_t)n) || O.fidx.reserve(ctx, n) ||
         O.Hs.reserve(ctx, R360_PGO_SLOT_H * mm) || O.bs.reserve(ctx, R360_PGO_SLOT_B * mm) ||
-        O.lin.reserve(ctx, R360_PGO_SLOT_LIN * mm) || O.cost.reserve(ctx, mm) ||
+        O.lin.reserve(ctx, R360_PGO_SLOT_LIN * mm) ||
         O.vfree.reserve(ctx, f) || O.vptr.reserve(ctx, f + 1) || O.rowptr.reserve(ctx, f + 1) || O.diag.reserve(ctx, f) ||
         O.b.reserve(ctx, 6 * f) || O.minv.reserve(ctx, 36 * f) || g->delta.reserve(ctx, 6 * f) || g->vec.reserve(ctx, 36 * f) ||
         O.ventry.reserve(ctx, e1) || O.vblk.reserve(ctx, e1) || O.colidx.reserve(ctx, nz) || O.vals.reserve(ctx, 36 * nz) ||
         g->partials.reserve(ctx, npart))
         return -1;
+    Staged H;
+    if (stage_edges(g, sel, H)) return -1;
     PgoDev& D = g->D;
-    D.n = n; D.m = m; D.nf = nf; D.nnzb = nnzb;
-    D.ij = O.ij.get(); D.Z = O.Z.get(); D.Om = O.Om.get(); D.vfree = O.vfree.get(); D.fidx = O.fidx.get();
+    D.nf = nf; D.nnzb = nnzb;
+    D.vfree = O.vfree.get(); D.fidx = O.fidx.get();
     D.vptr = O.vptr.get(); D.ventry = O.ventry.get(); D.vblk = O.vblk.get(); D.rowptr = O.rowptr.get();
     D.colidx = O.colidx.get(); D.diag = O.diag.get(); D.Hs = O.Hs.get(); D.bs = O.bs.get(); D.lin = O.lin.get();
-    D.cost = O.cost.get(); D.vals = O.vals.get(); D.b = O.b.get(); D.minv = O.minv.get();
-    std::vector<double> P(12 * (size_t)n), Z(12 * (size_t)m);
-    std::vector<int2> ij(m);
-    for (int v = 0; v < n; ++v) pose12(&g->poses[16 * (size_t)v], &P[12 * (size_t)v]);
-    for (int e = 0; e < m; ++e) {
-        pose12(&g->Z[16 * (size_t)e], &Z[12 * (size_t)e]);
-        ij[e] = make_int2(g->ij[2 * e], g->ij[2 * e + 1]);
-    }
+    D.vals = O.vals.get(); D.b = O.b.get(); D.minv = O.minv.get();
     hipStream_t st = ctx->stream;
-    if (upload(st, g->pose[0].get(), P) || upload(st, D.Z, Z) || upload(st, D.ij, ij) || upload(st, D.Om, g->Om) ||
-        upload(st, D.fidx, S.fidx) || upload(st, D.vfree, S.vfree) || upload(st, D.vptr, S.vptr) ||
+    if (upload(st, D.fidx, S.fidx) || upload(st, D.vfree, S.vfree) || upload(st, D.vptr, S.vptr) ||
         upload(st, D.ventry, S.ventry) || upload(st, D.vblk, S.vblk) || upload(st, D.rowptr, S.rowptr) ||
         upload(st, D.colidx, S.colidx) || upload(st, D.diag, S.diag))
         return -1;
@@ -281,6 +337,79 @@ extern "C" int r360_graph_add_edge(r360_graph* g, int from, int to, const double
     g->Z.insert(g->Z.end(), rel, rel + 16);
     for (int r = 0; r < 6; ++r)
         for (int c = 0; c < 6; ++c) g->Om.push_back((info[r * 6 + c] + info[c * 6 + r]) / 2);
+    g->kind.push_back(g->def_kind);
+    g->kdelta.push_back(g->def_delta);
+    g->active.push_back(1);
+    return 0;
+}
+
+namespace {
+int check_kernel(int kind, double delta) {
+    CHECK_ARG(kind == R360_GRAPH_KERNEL_NONE || kind == R360_GRAPH_KERNEL_HUBER || kind == R360_GRAPH_KERNEL_CAUCHY,
+              "graph: the robust kernel is R360_GRAPH_KERNEL_NONE, _HUBER or _CAUCHY");
+    CHECK_ARG(std::isfinite(delta) && delta > 0.0, "graph: the robust kernel's delta must be finite and positive");
+    return 0;
+}
+}  // namespace
+
+extern "C" int r360_graph_set_default_kernel(r360_graph* g, int kind, double delta) {
+    CHECK_ARG(g, "null arg");
+    if (int rc = check_kernel(kind, delta)) return rc;
+    g->def_kind = kind;
+    g->def_delta = delta;
+    return 0;
+}
+
+extern "C" int r360_graph_set_edge_kernel(r360_graph* g, int edge, int kind, double delta) {
+    CHECK_ARG(g, "null arg");
+    CHECK_ARG(edge >= 0 && edge < (int)g->active.size(), "graph: no such edge");
+    if (int rc = check_kernel(kind, delta)) return rc;
+    g->kind[edge] = kind;
+    g->kdelta[edge] = delta;
+    return 0;
+}
+
+extern "C" int r360_graph_get_edge_kernel(const r360_graph* g, int edge, int* kind, double* delta) {
+    CHECK_ARG(g, "null arg");
+    CHECK_ARG(edge >= 0 && edge < (int)g->active.size(), "graph: no such edge");
+    if (kind) *kind = g->kind[edge];
+    if (delta) *delta = g->kdelta[edge];
+    return 0;
+}
+
+extern "C" int r360_graph_set_edge_active(r360_graph* g, int edge, int active) {
+    CHECK_ARG(g, "null arg");
+    CHECK_ARG(edge >= 0 && edge < (int)g->active.size(), "graph: no such edge");
+    g->active[edge] = active ? 1 : 0;
+    return 0;
+}
+
+extern "C" int r360_graph_get_edge_active(const r360_graph* g, int edge, int* active) {
+    CHECK_ARG(g, "null arg");
+    CHECK_ARG(edge >= 0 && edge < (int)g->active.size(), "graph: no such edge");
+    if (active) *active = g->active[edge];
+    return 0;
+}
+
+extern "C" int r360_graph_edge_stats(r360_graph* g, double* chi2, double* weight, int cap, int* n) {
+    CHECK_ARG(g && n, "null arg");
+    const int m = (int)g->active.size();
+    *n = m;
+    if ((!chi2 && !weight) || m == 0) return 0;
+    if (cap < m) { r360_set_error("graph: capacity %d < %d edges", cap, m); return -4; }
+    if (bind_device(g->ctx->device)) return -1;
+    std::vector<int> sel(m);
+    std::iota(sel.begin(), sel.end(), 0);   // every edge, the inactive ones too: they report their chi2
+    Staged H;
+    if (stage_edges(g, sel, H)) return -1;
+    if (launch_pgo_linearise(g->ctx->stream, g->D, g->pose[0].get(), true, g->partials.get(), &g->d_out.get()->F)) return -1;
+    if (ctx_wait(g->ctx)) return -1;
+    if (chi2) R360_HIP(hipMemcpy(chi2, g->D.chi2, sizeof(double) * m, hipMemcpyDeviceToHost));
+    if (weight) {
+        R360_HIP(hipMemcpy(weight, g->D.wgt, sizeof(double) * m, hipMemcpyDeviceToHost));
+        for (int e = 0; e < m; ++e)
+            if (!g->active[e]) weight[e] = 0.0;
+    }
     return 0;
 }
 
@@ -318,12 +447,12 @@ extern "C" int r360_graph_optimize(r360_graph* g, const r360_graph_params* param
     if (int rc = check_params(&p)) return rc;
     r360_graph_stats st;
     memset(&st, 0, sizeof st);
-    const int m = (int)(g->ij.size() / 2);
+    const std::vector<int> sel = active_edges(g);
     int nfree = 0;
     for (char f : g->fixed) nfree += f ? 0 : 1;
-    if (nfree == 0 || m == 0) {   // nothing to move (a free vertex without an edge is caught below)
+    if (nfree == 0 || sel.empty()) {   // nothing to move (a free vertex without an edge is caught below)
         Structure S;
-        if (int rc = build_structure(g, S)) return rc;
+        if (int rc = build_structure(g, sel, S)) return rc;
         if (stats) *stats = st;
         return 0;
     }
@@ -477,8 +606,16 @@ extern "C" int r360_graph_solve(r360_graph* g, const r360_graph_params* params, 
 extern "C" int r360_graph_save(const r360_graph* g, const char* path) {
     CHECK_ARG(g && path, "null arg");
     std::vector<int> fixed(g->fixed.begin(), g->fixed.end());
-    return r360_g2o_write(path, (int)g->fixed.size(), g->poses.data(), fixed.data(), (int)(g->ij.size() / 2), g->ij.data(),
-                          g->Z.data(), g->Om.data());
+    const std::vector<int> sel = active_edges(g);
+    std::vector<int> ij;
+    std::vector<double> Z, Om;
+    for (int e : sel) {   // the active edges alone: the file is the graph that gets optimised
+        ij.insert(ij.end(), &g->ij[2 * (size_t)e], &g->ij[2 * (size_t)e] + 2);
+        Z.insert(Z.end(), &g->Z[16 * (size_t)e], &g->Z[16 * (size_t)e] + 16);
+        Om.insert(Om.end(), &g->Om[36 * (size_t)e], &g->Om[36 * (size_t)e] + 36);
+    }
+    return r360_g2o_write(path, (int)g->fixed.size(), g->poses.data(), fixed.data(), (int)sel.size(), ij.data(), Z.data(),
+                          Om.data());
 }
 
 extern "C" int r360_graph_load(r360_graph* g, const char* path) {
@@ -495,5 +632,8 @@ extern "C" int r360_graph_load(r360_graph* g, const char* path) {
     g->ij = ij;
     g->Z = Z;
     g->Om = Om;
+    g->kind.assign(ne, g->def_kind);
+    g->kdelta.assign(ne, g->def_delta);
+    g->active.assign(ne, 1);
     return 0;
 }

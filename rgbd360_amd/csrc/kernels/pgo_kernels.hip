@@ -1,9 +1,10 @@
 // pgo_kernels.hip — pose-graph optimisation (the reference's GraphOptimizer.h over g2o, restated and unpinned;
 // statement: tests/pgo_model.py) on gfx950, fp64 throughout.
 //
-//   k_pgo_linearise   one lane per edge: e, the Jacobians' 3x3 blocks, Omega e, the four products Ja^T Omega Jc, the
-//                     two vectors Ja^T Omega e and e^T Omega e into the edge's slots; the cost-only form writes the
-//                     last alone
+//   k_pgo_linearise   one lane per active edge: e, c = e^T Omega e, the edge's robust kernel (none, Huber, Cauchy:
+//                     rho(c) and w = rho'(c)), the Jacobians' 3x3 blocks, w Omega e, the four products
+//                     Ja^T (w Omega) Jc and the two vectors Ja^T (w Omega) e into the edge's slots; the cost-only
+//                     form writes rho, c and w alone
 //   k_pgo_sum / final the cost: workgroup records, then one wave sums them, both in a fixed order
 //   k_pgo_assemble    one wave per free vertex gathers its slots in edge order into the block-CSR rows of H and b
 //   k_pgo_norms       max diag(H) and max |b| (a maximum has no order)
@@ -167,8 +168,33 @@ __global__ void __launch_bounds__(LIN_TPB) k_pgo_linearise(PgoDev D, const doubl
     double f = 0.0;
 #pragma unroll
     for (int r = 0; r < 6; ++r) f += e[r] * Oe[r];
-    D.cost[k] = f;
+    // the robust kernel (g2o's RobustKernelHuber / RobustKernelCauchy on c = f, delta on sqrt(c)): rho(c) is the
+    // edge's cost, w = rho'(c) scales Omega e and Omega.  Without a kernel w = 1.0 and the products below are
+    // bit for bit those of the unscaled Omega.
+    double w = 1.0, rho = f;
+    const int kind = D.kind[k];
+    if (kind != R360_GRAPH_KERNEL_NONE) {
+        const double dl = D.kdelta[k], d2 = dl * dl;
+        if (kind == R360_GRAPH_KERNEL_CAUCHY) {
+            const double q = f / d2;
+            w = 1.0 / (1.0 + q);
+            rho = d2 * log1p(q);
+        } else if (f > d2) {
+            const double s = sqrt(f);
+            w = dl / s;
+            rho = 2.0 * dl * s - d2;
+        }
+    }
+    D.cost[k] = rho;
+    D.chi2[k] = f;
+    D.wgt[k] = w;
     if (COST_ONLY) return;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        Oe[r] *= w;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) Om[r][c] *= w;
+    }
 
     const M3 Jr = jr_inv(e + 3);
     const M3 RZt = transpose(RZ);

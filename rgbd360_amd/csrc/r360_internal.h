@@ -396,17 +396,19 @@ int launch_gicp_pass(hipStream_t st, const GicpCloud& S, const GicpCloud& T, con
 int launch_gicp_sum(hipStream_t st, const double* v, size_t n, double* partials, double* sums);
 
 // ------------------------------------------------------------------ pose-graph optimisation (kernels/pgo_kernels.hip, host/pgo.cpp)
-constexpr int R360_PGO_SLOT_H = 144;    // per-edge slot: the four 6x6 products Ja^T Omega Jc, (a, c) in (i, j) x (i, j)
-constexpr int R360_PGO_SLOT_B = 12;     // the two 6-vectors Ja^T Omega e
-constexpr int R360_PGO_SLOT_LIN = 57;   // e (6), Omega e (6), then R_E, Jr^-1, -R_Z^T, R_Z^T [t_B]x, -Jr^-1 R_B^T (9 each)
+constexpr int R360_PGO_SLOT_H = 144;    // per-edge slot: the four 6x6 products Ja^T (w Omega) Jc, (a, c) in (i, j) x (i, j)
+constexpr int R360_PGO_SLOT_B = 12;     // the two 6-vectors Ja^T (w Omega) e
+constexpr int R360_PGO_SLOT_LIN = 57;   // e (6), w Omega e (6), then R_E, Jr^-1, -R_Z^T, R_Z^T [t_B]x, -Jr^-1 R_B^T (9 each)
 constexpr int R360_PGO_CG1_TPB = 1024;  // the single-workgroup PCG's threads
 constexpr int R360_PGO_CG1_LDS = 65536 - 512;   // dynamic LDS it may take: four vectors of 6 n_free doubles
 constexpr int R360_PGO_CGM_TPB = 192;   // multi-launch PCG: 32 block rows per workgroup
 constexpr int R360_PGO_MAXB = 256;      // workgroups (= partial sums) of the cost reduction at most
 // What the kernels read of one optimise call: every array is sized by the graph alone and rebuilt per call.
 struct PgoDev {
-    int n = 0, m = 0, nf = 0, nnzb = 0;   // vertices, edges, free vertices, blocks of H
+    int n = 0, m = 0, nf = 0, nnzb = 0;   // vertices, edges (the active ones, in edge order), free vertices, blocks of H
     int2* ij = nullptr;           // [m] the edge's vertices
+    int* kind = nullptr;          // [m] the edge's robust kernel, R360_GRAPH_KERNEL_*
+    double* kdelta = nullptr;     // [m] and its width delta > 0
     double* Z = nullptr;          // [m][12] row-major 3x4 measurement
     double* Om = nullptr;         // [m][36] information, symmetric
     int* vfree = nullptr;         // [nf] the free vertices
@@ -420,7 +422,9 @@ struct PgoDev {
     double* Hs = nullptr;         // [m][R360_PGO_SLOT_H]
     double* bs = nullptr;         // [m][R360_PGO_SLOT_B]
     double* lin = nullptr;        // [m][R360_PGO_SLOT_LIN]
-    double* cost = nullptr;       // [m] e^T Omega e
+    double* cost = nullptr;       // [m] rho(c), c = e^T Omega e
+    double* chi2 = nullptr;       // [m] c
+    double* wgt = nullptr;        // [m] w = rho'(c)
     double* vals = nullptr;       // [nnzb][36] row-major blocks of H
     double* b = nullptr;          // [6 nf]
     double* minv = nullptr;       // [nf][36] (H_kk + lambda I)^-1

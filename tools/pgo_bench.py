@@ -3,9 +3,10 @@
 2049-vertex graph of the same recipe in the multi-launch form: device events on the context's stream around the whole
 call (which includes its host decisions and read-backs), the median of --reps calls after --warmup, with min and max,
 and the numpy model's wall time on the same inputs beside them.  At 257 vertices both CG forms are timed.  There is
-no reference timing (g2o is not part of the reference tree), so no figure here is a pass / fail bar.
+no reference timing (g2o is not part of the reference tree), so no figure here is a pass / fail bar.  With
+--robust-delta D one more row follows: the 257-vertex graph with a Huber kernel of width D on its loop edges.
 
-    python tools/pgo_bench.py [--json out.json]
+    python tools/pgo_bench.py [--json out.json] [--robust-delta 1]
 """
 import argparse
 import json
@@ -32,6 +33,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-model", action="store_true")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--robust-delta", type=float, default=None)
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -39,9 +41,11 @@ def main():
     ctx = R.Context(0)
     stream = torch.cuda.ExternalStream(int(R.lib().r360_ctx_stream(ctx.h)))
     res = {"reps": a.reps, "warmup": a.warmup, "cases": []}
-    runs = [("n65", 0), ("n257", 1), ("n257", 2), ("n513", 0), ("n2049", 2)]
+    runs = [("n65", 0, None), ("n257", 1, None), ("n257", 2, None), ("n513", 0, None), ("n2049", 2, None)]
+    if a.robust_delta is not None:
+        runs.append(("n257", 1, a.robust_delta))
     model_s = {}
-    for name, form in runs:
+    for name, form, huber in runs:
         n = int(name[1:])
         if n in Cs.SIZED:
             g = Cs.build_sized(n, *Cs.SIZED[n])[0]
@@ -51,6 +55,7 @@ def main():
         for T in g.poses:
             pg.addVertex(T)
         for (i, j, Z, Om) in g.edges:
+            pg.setRobustKernel(R.GRAPH_KERNEL_HUBER if huber and abs(i - j) != 1 else R.GRAPH_KERNEL_NONE, huber or 1.0)
             pg.addEdge(i, j, Z, Om)
         prm = R.GraphParams.default(cg_form=form)
         ms, st = [], None
@@ -69,11 +74,12 @@ def main():
             t0 = time.perf_counter()
             M.optimize(g)
             model_s[name] = time.perf_counter() - t0
-        row = {"case": name, "vertices": n, "edges": len(g.edges), "cg_form": st.cg_form, "status": st.status,
+        row = {"case": name if huber is None else f"{name} huber {huber:g} on the loop edges", "vertices": n,
+               "edges": len(g.edges), "cg_form": st.cg_form, "status": st.status,
                "iterations": st.iterations, "trials": st.trials, "cg_iterations": st.cg_iterations,
                "cg_iterations_max": st.cg_iterations_max, "F_initial": st.F_initial, "F_final": st.F_final,
                "ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)),
-               "model_s": model_s.get(name)}
+               "model_s": model_s.get(name) if huber is None else None}
         res["cases"].append(row)
         print(json.dumps(row), flush=True)
     ctx.close()
