@@ -572,6 +572,21 @@ int r360_frame_get_regions(r360_frame* f, int sensor, r360_region* out, int cap,
  * ("plane segmentation capacity exceeded (code ...)"); *err_code (optional) receives the stage's error bits. */
 int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const float* nrm, int nrm_comps, const uint8_t* rgb4,
                             int* err_code);
+/* The same for n <= 8 frames of one context and size as one batch of the stage's launcher (the batch a plane queue or
+ * r360_frames_build forms): xyz4, nrm and rgb4 hold the frames' fields one after the other, err_codes[n] (optional)
+ * receives each frame's error bits.  Returns < 0 if any frame's stage failed. */
+int r360_frames_segment_eval(r360_frame* const* frames, int n, const float* xyz4, const float* nrm, int nrm_comps,
+                             const uint8_t* rgb4, int* err_codes);
+/* Parity hook: the refinement's states [8][h][w] after its two sweeps (-1 no label, -2 non-planar label, m >= 0
+ * model m of the sensor) as the frame's last build or segment_eval left them, and the wavefront sweeps' flags[24]:
+ * [s] != 0: the single-wave fallback redid sensor s's second sweep, [8 + s]: re-runs of its second sweep after wrap
+ * pushes, [16 + s] != 0: its pipelined first sweep gave up and the fallback redid both sweeps. */
+int r360_frame_get_refine_states(r360_frame* f, int8_t* state, int* flags);
+/* Test hook: the frame builds that follow hand the sensors of sensor_mask (bit 8 * frame-in-batch + sensor) to the
+ * single-wave fallback kernel after their wavefront sweeps, as if the second sweep's re-runs had run out at the middle
+ * row (first_sweep = 0) or the pipelined first sweep had given up (first_sweep != 0); the results must not change.
+ * No field makes a build take that path.  0 switches it off.  Process-wide, not for concurrent builds. */
+void r360_refine_force_fallback(uint64_t sensor_mask, int first_sweep);
 /* Region `region` of `sensor` as the segmentation stage left it, before the hull prefilter and the host assembly:
  * stats[20] = the final inliers' exact moments (PlaneOut::stats: n, s1[3], s2[6] as (low, high) 64-bit words,
  * c[4]), bounds[6] = local-frame min xyz, max xyz, and the traced contour's points in trace order from the device

@@ -384,6 +384,9 @@ _SIGS = [
     ("r360_frame_get_labels", C.c_int, [_P, _IP, _IP]),
     ("r360_frame_get_regions", C.c_int, [_P, C.c_int, C.POINTER(Region), C.c_int, _IP]),
     ("r360_frame_segment_eval", C.c_int, [_P, _FP, _FP, C.c_int, _P, _IP]),
+    ("r360_frames_segment_eval", C.c_int, [C.POINTER(C.c_void_p), C.c_int, _FP, _FP, C.c_int, _P, _IP]),
+    ("r360_frame_get_refine_states", C.c_int, [_P, _P, _IP]),
+    ("r360_refine_force_fallback", None, [C.c_uint64, C.c_int]),
     ("r360_frame_get_region_detail", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int64), _FP, _FP, C.c_int, _IP]),
     ("r360_comm_unique_id", C.c_int, [_P]),
     ("r360_comm_init", C.c_int, [C.c_int, C.c_int, C.c_int, _P, C.POINTER(_P)]),
@@ -1026,6 +1029,16 @@ class Frame360:
             raise e
         return rc
 
+    def refine_states(self):
+        """Parity hook (r360_frame_get_refine_states): the refinement's states int8 [8, h, w] after its sweeps (-1 no
+        label, -2 non-planar label, m >= 0 model m) and the wavefront sweeps' 24 flag words ([s]: the single-wave
+        fallback redid sensor s, [8 + s]: re-runs of its second sweep, [16 + s]: its first sweep gave up)."""
+        state = np.zeros((8, self.rows // 2, self.cols // 2), np.int8)
+        flags = np.zeros(24, np.int32)
+        _check(lib().r360_frame_get_refine_states(self.h, state.ctypes.data, flags.ctypes.data_as(_IP)),
+               "get_refine_states")
+        return state, flags
+
     def region_detail(self, sensor: int, region: int) -> dict:
         """Region `region` of `sensor` before the hull prefilter and the host assembly: the exact moments of its final
         inliers (Python integers: n, s1[3], s2[6] = xx xy xz yy yz zz, c[4]), its local-frame bounds and its traced
@@ -1222,6 +1235,35 @@ def frames_build(frames, flags: int = None):
         flags = BUILD_UNDISTORT | BUILD_CLOUD | BUILD_PLANES | BUILD_SPHERE | BUILD_PYRAMID
     arr = (C.c_void_p * len(frames))(*[f.h for f in frames])
     _check(lib().r360_frames_build(arr, len(frames), flags), "r360_frames_build")
+
+
+def refine_force_fallback(sensor_mask: int = 0, first_sweep: bool = False):
+    """Test hook (r360_refine_force_fallback): the builds that follow hand the sensors of sensor_mask (bit 8 * frame in
+    batch + sensor) to the single-wave fallback kernel after their wavefront sweeps; 0 switches it off."""
+    lib().r360_refine_force_fallback(sensor_mask, int(first_sweep))
+
+
+def frames_segment_eval(frames, xyz4: np.ndarray, nrm: np.ndarray, rgb4: np.ndarray):
+    """Parity hook (r360_frames_segment_eval): Frame360.segment_eval of up to 8 frames of one context and size as one
+    batch of the stage's launcher.  xyz4 [n, 8, h, w, 4], nrm [n, 8, h, w, 3 or 4], rgb4 [n, 8, h, w, 4].  Returns the
+    frames' error bits; a capacity error of any frame raises RuntimeError with them in its `codes` attribute."""
+    n = len(frames)
+    h, w = frames[0].rows // 2, frames[0].cols // 2
+    xyz4 = np.ascontiguousarray(xyz4, np.float32)
+    nrm = np.ascontiguousarray(nrm, np.float32)
+    rgb4 = np.ascontiguousarray(rgb4, np.uint8)
+    if xyz4.shape != (n, 8, h, w, 4) or nrm.shape[:4] != (n, 8, h, w) or nrm.shape[4] not in (3, 4) or \
+            rgb4.shape != (n, 8, h, w, 4):
+        raise ValueError(f"frames_segment_eval: fields of {n} x 8 x {h} x {w} expected")
+    arr = (C.c_void_p * n)(*[f.h for f in frames])
+    codes = np.zeros(n, np.int32)
+    rc = lib().r360_frames_segment_eval(arr, n, _fptr(xyz4), _fptr(nrm), nrm.shape[4], _vptr(rgb4),
+                                        codes.ctypes.data_as(_IP))
+    if rc < 0:
+        e = RuntimeError(f"frames_segment_eval failed ({rc}): {lib().r360_last_error().decode()}")
+        e.codes = codes
+        raise e
+    return codes
 
 
 def register(ctx: "Context", ref: "Frame360", trg: "Frame360", guess=None, params: "IcpParams | None" = None,

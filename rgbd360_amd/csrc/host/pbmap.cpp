@@ -1737,72 +1737,117 @@ extern "C" int r360_frame_get_regions(r360_frame* f, int sensor, r360_region* ou
     return 0;
 }
 
-// Parity hook (rgbd360_hip.h): the segmentation stage of a build on given points, normals and colours.  The launcher,
-// buffers, stream and voxel scratch are those planes_enqueue uses for a lone frame (kernel by kernel, no graph); only
-// the stage's inputs come from the caller, and the host assembly is left out (the frame's PbMap is empty).
-extern "C" int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const float* nrm, int nrm_comps,
-                                       const uint8_t* rgb4, int* err_code) {
-    CHECK_ARG(f && xyz4 && nrm && rgb4 && (nrm_comps == 3 || nrm_comps == 4), "segment_eval: bad arguments");
-    if (bind_device(f->ctx->device)) return -1;
-    CHECK_ARG(f->rows > 0, "a sphere-only frame has no sensor images");
-    planes_join(f);   // a previous build's assembly (or a plane queue's batch) still using the buffers
-    if (plane_bufs_alloc(f)) return -1;
-    r360_ctx* ctx = f->ctx;
-    hipStream_t st = ctx->stream;
-    PlaneBufs& P = f->pl;
-    const int w = P.w, h = P.h, rows = f->rows, cols = f->cols;
-    const size_t T = 8 * (size_t)w * h;
-    // the colours as the BGR images' centre pixels (2 r + 1, 2 c + 1), which launch_rgb reads
-    std::vector<uint8_t> bgr((size_t)8 * rows * cols * 3, 0);
-    for (int s = 0; s < 8; ++s)
-        for (int r = 0; r < h; ++r)
-            for (int c = 0; c < w; ++c) {
-                const uint8_t* q = rgb4 + 4 * (((size_t)s * h + r) * w + c);
-                uint8_t* d = bgr.data() + (((size_t)s * rows + 2 * r + 1) * cols + 2 * c + 1) * 3;
-                d[0] = q[2]; d[1] = q[1]; d[2] = q[0];
-            }
-    std::vector<float> n4;
-    if (nrm_comps == 3) {
-        n4.resize(4 * T);
-        for (size_t i = 0; i < T; ++i) {
-            for (int k = 0; k < 3; ++k) n4[4 * i + k] = nrm[3 * i + k];
-            n4[4 * i + 3] = 0.f;
-        }
+// Parity hook (rgbd360_hip.h): the segmentation stage of a build on given points, normals and colours, of n frames
+// of one context and size as one batch.  The launcher, buffers and stream are those of a build (a lone frame's as
+// planes_enqueue's kernel-by-kernel path, more as r360_frames_build's batch with its voxel scratch slots); only the
+// stage's inputs come from the caller, and the host assembly is left out (the frames' PbMaps are empty).
+extern "C" int r360_frames_segment_eval(r360_frame* const* frames, int n, const float* xyz4, const float* nrm,
+                                        int nrm_comps, const uint8_t* rgb4, int* err_codes) {
+    CHECK_ARG(frames && n >= 1 && n <= R360_PLANE_BATCH && xyz4 && nrm && rgb4 && (nrm_comps == 3 || nrm_comps == 4),
+              "segment_eval: bad arguments");
+    for (int i = 0; i < n; ++i) {
+        CHECK_ARG(frames[i] && frames[i]->rows > 0, "a sphere-only frame has no sensor images");
+        CHECK_ARG(frames[i]->ctx == frames[0]->ctx && frames[i]->rows == frames[0]->rows && frames[i]->cols == frames[0]->cols,
+                  "segment_eval: frames of one context and size expected");
+        for (int j = 0; j < i; ++j) CHECK_ARG(frames[j] != frames[i], "segment_eval: a frame is listed twice");
     }
-    if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipEventSynchronize(e));   // a split upload's copy in flight
-    R360_HIP(hipStreamSynchronize(st));
-    f->bgr_split = false;
-    R360_HIP(hipMemcpy(f->d_bgr, bgr.data(), bgr.size(), hipMemcpyHostToDevice));
-    R360_HIP(hipMemcpy(P.cloud, xyz4, sizeof(float4) * T, hipMemcpyHostToDevice));
-    R360_HIP(hipMemcpy(P.nrm, nrm_comps == 3 ? n4.data() : nrm, sizeof(float4) * T, hipMemcpyHostToDevice));
-    const PlaneGeom G = plane_geom(f);
-    long cells, entries, groups;
-    vox_scratch_need(G, &cells, &entries, &groups);
-    if (ctx_vhash_reserve(ctx, cells, entries, groups)) return -1;
+    r360_ctx* ctx = frames[0]->ctx;
+    if (bind_device(ctx->device)) return -1;
+    hipStream_t st = ctx->stream;
+    if ((int)ctx->bvox.size() < R360_PLANE_BATCH - 1) ctx->bvox.resize(R360_PLANE_BATCH - 1);
     PlaneBatch B;
     std::memset(&B, 0, sizeof B);
-    B.f[0] = plane_dev(f, VoxScratch{ctx->d_vhash, (unsigned long long)ctx->vhash_cap, ctx->d_vlist, ctx->d_vcnt});
-    P.ticket.reset();
-    delete f->pbmap;
-    f->pbmap = nullptr;
-    delete f->local;
-    f->local = nullptr;
-    f->built = 0;   // the images are not the uploaded ones any more
-    if (launch_segment_inputs(B, 1, G, st)) return -1;
-    if (launch_segmentation(B, 1, G, st, ctx, nullptr)) return -1;
-    if (launch_plane_publish(B, 1, st)) return -1;
-    R360_HIP(hipEventRecord(P.done, st));
-    R360_HIP(hipStreamSynchronize(st));
-    f->built = R360_BUILD_CLOUD | R360_BUILD_PLANES;
-    if (err_code) *err_code = P.h_nmodels[8];
-    if (planes_capacity_ok(f)) {
-        P.worker_rc = -1;
-        P.worker_err = r360_last_error();
-        return -1;
+    PlaneGeom G{};
+    for (int i = 0; i < n; ++i) {
+        r360_frame* f = frames[i];
+        planes_join(f);   // a previous build's assembly (or a plane queue's batch) still using the buffers
+        if (plane_bufs_alloc(f)) return -1;
+        PlaneBufs& P = f->pl;
+        const int w = P.w, h = P.h, rows = f->rows, cols = f->cols;
+        const size_t T = 8 * (size_t)w * h;
+        const float* fx = xyz4 + 4 * T * i;
+        const float* fn = nrm + (size_t)nrm_comps * T * i;
+        const uint8_t* fc = rgb4 + 4 * T * i;
+        // the colours as the BGR images' centre pixels (2 r + 1, 2 c + 1), which launch_rgb reads
+        std::vector<uint8_t> bgr((size_t)8 * rows * cols * 3, 0);
+        for (int s = 0; s < 8; ++s)
+            for (int r = 0; r < h; ++r)
+                for (int c = 0; c < w; ++c) {
+                    const uint8_t* q = fc + 4 * (((size_t)s * h + r) * w + c);
+                    uint8_t* d = bgr.data() + (((size_t)s * rows + 2 * r + 1) * cols + 2 * c + 1) * 3;
+                    d[0] = q[2]; d[1] = q[1]; d[2] = q[0];
+                }
+        std::vector<float> n4;
+        if (nrm_comps == 3) {
+            n4.resize(4 * T);
+            for (size_t k = 0; k < T; ++k) {
+                for (int q = 0; q < 3; ++q) n4[4 * k + q] = fn[3 * k + q];
+                n4[4 * k + 3] = 0.f;
+            }
+        }
+        if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipEventSynchronize(e));   // a split upload's copy in flight
+        R360_HIP(hipStreamSynchronize(st));
+        f->bgr_split = false;
+        R360_HIP(hipMemcpy(f->d_bgr, bgr.data(), bgr.size(), hipMemcpyHostToDevice));
+        R360_HIP(hipMemcpy(P.cloud, fx, sizeof(float4) * T, hipMemcpyHostToDevice));
+        R360_HIP(hipMemcpy(P.nrm, nrm_comps == 3 ? n4.data() : fn, sizeof(float4) * T, hipMemcpyHostToDevice));
+        G = plane_geom(f);
+        long cells, entries, groups;
+        vox_scratch_need(G, &cells, &entries, &groups);
+        if (ctx_vhash_reserve(ctx, cells, entries, groups)) return -1;
+        VoxScratch vs{ctx->d_vhash, (unsigned long long)ctx->vhash_cap, ctx->d_vlist, ctx->d_vcnt};
+        if (i > 0) {
+            if (vox_slot_reserve(ctx->bvox[i - 1], G, st)) return -1;
+            vs = ctx->bvox[i - 1].v;
+        }
+        B.f[i] = plane_dev(f, vs);
+        P.ticket.reset();
+        delete f->pbmap;
+        f->pbmap = nullptr;
+        delete f->local;
+        f->local = nullptr;
+        f->built = 0;   // the images are not the uploaded ones any more
     }
-    P.worker_rc = 0;
-    P.worker_err.clear();
-    f->pbmap = new PbMapHost;
+    if (launch_segment_inputs(B, n, G, st)) return -1;
+    if (launch_segmentation(B, n, G, st, ctx, nullptr)) return -1;
+    if (launch_plane_publish(B, n, st)) return -1;
+    for (int i = 0; i < n; ++i) R360_HIP(hipEventRecord(frames[i]->pl.done, st));
+    R360_HIP(hipStreamSynchronize(st));
+    int rc = 0;
+    for (int i = 0; i < n; ++i) {
+        r360_frame* f = frames[i];
+        PlaneBufs& P = f->pl;
+        f->built = R360_BUILD_CLOUD | R360_BUILD_PLANES;
+        if (err_codes) err_codes[i] = P.h_nmodels[8];
+        if (planes_capacity_ok(f)) {
+            P.worker_rc = -1;
+            P.worker_err = r360_last_error();
+            rc = -1;
+            continue;
+        }
+        P.worker_rc = 0;
+        P.worker_err.clear();
+        f->pbmap = new PbMapHost;
+    }
+    return rc;
+}
+
+extern "C" int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const float* nrm, int nrm_comps,
+                                       const uint8_t* rgb4, int* err_code) {
+    CHECK_ARG(f, "segment_eval: bad arguments");
+    return r360_frames_segment_eval(&f, 1, xyz4, nrm, nrm_comps, rgb4, err_code);
+}
+
+// Parity hook: the refinement's raster states [8][h][w] as the last build or segment_eval left them (k_vox_hash reads
+// them after the refinement, nothing writes them), and the wavefront sweeps' 24 flag words (PlaneBufs::rflag: per
+// sensor the row + 1 k_refine_fb resumed at, the second sweep's re-runs, and whether the first sweep gave up).
+extern "C" int r360_frame_get_refine_states(r360_frame* f, int8_t* state, int* flags) {
+    CHECK_ARG(state && flags, "get_refine_states: null output");
+    if (int rc = ready(f)) return rc;
+    CHECK_ARG(f->pl.cloud, "frame planes were loaded, not built: no refinement states");
+    PlaneBufs& P = f->pl;
+    R360_HIP(hipMemcpy(state, P.state, 8 * (size_t)P.w * P.h, hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(flags, P.rflag, sizeof(int) * 24, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -10,7 +10,8 @@
 //   k_refine       the two raster sweeps of refine(): one wave per sensor walks the rows; within a row
 //                  the left-to-right (right-to-left) label chains are resolved with wave scans over
 //                  per-lane chunk summaries; closeness to every model is precomputed per pixel as a
-//                  bit mask (k_refine_init)
+//                  bit mask (k_refine_prep<true>, in the pass that skews the wavefront sweeps' inputs; the refined
+//                  labels come out of the pass that unskews their result, k_refine_finish)
 //   k_gm<true>     final inlier moments (rig frame) + colour sums + bounds per refined region (folded by k_nbmask)
 //   k_trace        findLabeledRegionBoundary (Moore-neighbour trace) over per-pixel neighbour masks
 //   k_vox_*        VoxelGrid of regions without a contour (Frame360.h:1017-1026): (region, voxel) hash
@@ -1085,34 +1086,65 @@ __global__ void __launch_bounds__(64) k_refine_p2(const PlaneBatch B, int w, int
 // flag is set and k_refine_fb redoes the second sweep with the single-wave kernel.  Without such a row every
 // pixel satisfies the sequential recurrences, so the states are the sequential sweep's bit for bit.
 //
-// Inputs in skewed layout (k_refine_skew): slot k * h + r of diagonal k holds pixel (r, k - r), so a step's
+// Inputs in skewed layout (k_refine_prep): slot k * h + r of diagonal k holds pixel (r, k - r), so a step's
 // loads are coalesced; code = state | static push conditions << 8.
 constexpr int RW_PF = 8;   // diagonals prefetched ahead
 
-__device__ __forceinline__ void d_refine_skew(const int8_t* __restrict__ S, const unsigned long long* __restrict__ MK, int w, int h,
-                              uint16_t* __restrict__ code, unsigned long long* __restrict__ msk, int* __restrict__ fb) {
-    // one thread per skewed slot (coalesced stores; the raster reads walk down-left diagonals, which reuse
-    // each cache line for the next diagonals); slots outside the image are never used
-    const long N = (long)w * h, SK = (long)(h + w - 1) * h, total = 8 * SK;
-    if (blockIdx.x == 0 && threadIdx.x < 24) fb[threadIdx.x] = 0;
-    for (long d = blockIdx.x * (long)blockDim.x + threadIdx.x; d < total; d += (long)gridDim.x * blockDim.x) {
-        const int s = (int)(d / SK);
-        const long q = d - (long)s * SK;
-        const int k = (int)(q / h), r = (int)(q - (long)k * h);
-        const int c = k - r;
-        if (c < 0 || c >= w) continue;
-        const int j = r * w + c;
-        const long i = (long)s * N + j;
+// One thread per pixel, raster order, grid (pixel chunks, 8 sensors): the pixel's skewed slot gets its state with the
+// two static push conditions, and its closeness mask.  No thread is spent on the slots outside the image, and only
+// the two skewed stores are scattered (a slot's neighbours in its diagonal are the pixels down-left and up-right, a
+// row apart: the cache lines fill over the next rows).
+// INIT (frame builds): k_refine_init in the same pass.  State and mask come from the labels, the models and the
+// cloud point as in d_refine_init and are written in raster order too (k_refine_fb reads both, k_vox_hash the state);
+// a neighbour's state is != -1 exactly where its label is >= 0, so the push conditions read the labels.
+// !INIT (r360_refine_eval): states and masks are given in raster order.
+template <bool INIT>
+__device__ __forceinline__ void d_refine_prep(const float4* __restrict__ cloud, const int* __restrict__ lab,
+                                              const PlaneModel* __restrict__ models, const int* __restrict__ nmodels,
+                                              int8_t* __restrict__ S, unsigned long long* __restrict__ MK, int w, int h,
+                                              uint16_t* __restrict__ code, unsigned long long* __restrict__ msk,
+                                              int* __restrict__ fb) {
+    const int s = blockIdx.y, N = w * h;
+    if (blockIdx.x == 0 && s == 0 && threadIdx.x < 24) fb[threadIdx.x] = 0;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const int r = j / w, c = j - r * w;
+    const long i = (long)s * N + j;
+    const long d = (long)s * (h + w - 1) * h + (long)(r + c) * h + r;
+    const int up = (r - 1) * w + c + 1, dn = c >= 1 ? (r + 1) * w + c - 1 : r * w + w - 1;
+    int st;
+    unsigned long long bits = 0;
+    bool c1 = r >= 1 && c <= w - 2, c2 = r <= h - 2;
+    if (INIT) {
+        const int* L8 = lab + (long)s * N;
+        const int L = L8[j];
+        const int nm = nmodels[s];
+        const PlaneModel* M = models + s * R360_MAX_MODELS;
+        st = L < 0 ? -1 : -2;
+        const float4 p = cloud[i];
+        for (int m = 0; m < nm; ++m) {
+            if (L >= 0 && M[m].label == L) st = m;
+            const double ptp = fabs((double)(M[m].v[0] * p.x + M[m].v[1] * p.y + M[m].v[2] * p.z + M[m].v[3]));
+            if (ptp < (double)0.02f) bits |= 1ull << m;
+        }
+        S[i] = (int8_t)st;
+        MK[i] = bits;
+        c1 = c1 && L8[up] >= 0;
+        c2 = c2 && L8[dn] >= 0;
+    } else {
         const int8_t* O = S + (long)s * N;
-        const bool c1 = r >= 1 && c <= w - 2 && O[(r - 1) * w + c + 1] != -1;
-        const bool c2 = r <= h - 2 && (c >= 1 ? O[(r + 1) * w + c - 1] != -1 : O[r * w + w - 1] != -1);
-        code[d] = (uint16_t)((uint8_t)O[j] | (c1 ? 0x100 : 0) | (c2 ? 0x200 : 0));
-        msk[d] = MK[i];
+        st = O[j];
+        bits = MK[i];
+        c1 = c1 && O[up] != -1;
+        c2 = c2 && O[dn] != -1;
     }
+    code[d] = (uint16_t)((uint8_t)(int8_t)st | (c1 ? 0x100 : 0) | (c2 ? 0x200 : 0));
+    msk[d] = bits;
 }
-__global__ void k_refine_skew(const PlaneBatch B, int w, int h) {
+template <bool INIT>
+__global__ void __launch_bounds__(256) k_refine_prep(const PlaneBatch B, int w, int h) {
     const PlaneDev& D = B.f[blockIdx.z];
-    d_refine_skew(D.state, D.mask, w, h, D.rcode, D.rmsk, D.rflag);
+    d_refine_prep<INIT>(D.cloud, D.lab, D.models, D.nmodels, D.state, D.mask, w, h, D.rcode, D.rmsk, D.rflag);
 }
 
 
@@ -1632,36 +1664,71 @@ __global__ void k_refine_unskew(const PlaneBatch B, int w, int h) {
 }
 
 
+// Frame builds: k_refine_unskew and k_refine_final in one pass, one thread per pixel (grid: pixel chunks, 8 sensors).
+// A sensor k_refine_fb redoes is left alone, labels included: one whose wrap push the re-runs did not settle
+// (fb[s]), and one whose pipelined first sweep gave up (fb[16 + s]; k_refine_fb then sweeps the raster states
+// k_refine_prep<true> wrote, which must still be the original ones).
+__device__ __forceinline__ void d_refine_finish(const int8_t* __restrict__ f2_all, int8_t* __restrict__ S_all,
+                                                const int* __restrict__ fb, const int* __restrict__ lab,
+                                                const PlaneModel* __restrict__ models, int* __restrict__ labf, int w,
+                                                int h) {
+    const int s = blockIdx.y, N = w * h;
+    if (fb[s] != 0 || fb[16 + s] != 0) return;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const int r = j / w, c = j - r * w;
+    const long i = (long)s * N + j;
+    const int st = f2_all[(long)s * (h + w - 1) * h + (long)(r + c) * h + r];
+    S_all[i] = (int8_t)st;
+    labf[i] = st >= 0 ? models[s * R360_MAX_MODELS + st].label : (st == -2 ? lab[i] : -1);
+}
+__global__ void __launch_bounds__(256) k_refine_finish(const PlaneBatch B, int w, int h) {
+    const PlaneDev& D = B.f[blockIdx.z];
+    d_refine_finish(D.rf2, D.state, D.rflag, D.lab, D.models, D.labf, w, h);
+}
+
+
 // The exact second sweep for a sensor whose wavefront saw the wrap push fire, first at target row r0 = fb - 1:
 // rows below r0 are exact (nothing they depend on fired), so rows 0..r0 get the first sweep's states back and
 // the single-wave sweep resumes at source row r0 + 1 (re-chaining a swept row leaves it unchanged).
-template <int K>
+// LABF (frame builds, after k_refine_finish): the refined labels of the sensors it redoes, as k_refine_final's.
+template <int K, bool LABF>
 __device__ __forceinline__ void d_refine_fb(const int8_t* __restrict__ f1_all, const int8_t* __restrict__ f2_all,
                                                  int8_t* __restrict__ S_all,
                                                  const unsigned long long* __restrict__ MK, const int* __restrict__ fb,
-                                                 int w, int h) {
+                                                 const int* __restrict__ lab, const PlaneModel* __restrict__ models,
+                                                 int* __restrict__ labf, int w, int h) {
     const int s = blockIdx.x;
+    const long N = (long)w * h, SK = (long)(h + w - 1) * h;
     if (fb[16 + s]) {   // the pipelined first sweep gave up: both sweeps from the original states
         refine_sweeps<K>(S_all, MK, w, h, s, 3);
-        return;
+    } else {
+        const int r0 = fb[s] - 1;
+        if (r0 < 0) return;
+        // rows 0..r0 from the first sweep, rows below from the wavefront's (exact) second sweep
+        for (long j = threadIdx.x; j < N; j += 64) {
+            const int r = (int)(j / w), c = (int)(j - (long)r * w);
+            S_all[s * N + j] = (r <= r0 ? f1_all : f2_all)[s * SK + (long)(r + c) * h + r];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        refine_sweeps<K>(S_all, MK, w, h, s, 2, r0 + 1);
     }
-    const int r0 = fb[s] - 1;
-    if (r0 < 0) return;
-    const long N = (long)w * h, SK = (long)(h + w - 1) * h;
-    // rows 0..r0 from the first sweep, rows below from the wavefront's (exact) second sweep
-    for (long j = threadIdx.x; j < N; j += 64) {
-        const int r = (int)(j / w), c = (int)(j - (long)r * w);
-        S_all[s * N + j] = (r <= r0 ? f1_all : f2_all)[s * SK + (long)(r + c) * h + r];
+    if (LABF) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        for (long j = threadIdx.x; j < N; j += 64) {
+            const int st = S_all[s * N + j];
+            labf[s * N + j] = st >= 0 ? models[s * R360_MAX_MODELS + st].label : (st == -2 ? lab[s * N + j] : -1);
+        }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    refine_sweeps<K>(S_all, MK, w, h, s, 2, r0 + 1);
 }
-template <int K>
+template <int K, bool LABF>
 __global__ void __launch_bounds__(64) k_refine_fb(const PlaneBatch B, int w, int h) {
     const PlaneDev& D = B.f[blockIdx.z];
-    d_refine_fb<K>(D.rf1, D.rf2, D.state, D.mask, D.rflag, w, h);
+    d_refine_fb<K, LABF>(D.rf1, D.rf2, D.state, D.mask, D.rflag, D.lab, D.models, D.labf, w, h);
 }
 
 
@@ -2310,6 +2377,37 @@ __global__ void __launch_bounds__(VOXH_TPB) k_hullpre(const PlaneBatch B) {
 }  // namespace
 
 
+// Test hook (r360_refine_force_fallback): sensors of a frame build handed to k_refine_fb although their wavefront
+// sweeps came out exact.  No field reaches k_refine_fb through a build: a wrap push's value never depends on another
+// row's wrap push (the chain that would carry it along the row also pushes it up by the ordinary way), so one re-run
+// settles every row, and the hand-off wait does not give up.  Bit 8 * frame + sensor of the mask; first_sweep: as after
+// a first sweep that gave up (both sweeps from the raster states), else as after the re-runs ran out at the middle row.
+static unsigned long long g_force_fb_mask = 0;
+static int g_force_fb_first = 0;
+
+namespace {
+__global__ void k_refine_force_fb(const PlaneBatch B, int w, int h, unsigned long long mask, int first_sweep) {
+    const int f = blockIdx.x, s = blockIdx.y;
+    if (!((mask >> (8 * f + s)) & 1ull)) return;
+    const PlaneDev& D = B.f[f];
+    int* fb = D.rflag;
+    if (!first_sweep) {
+        if (threadIdx.x == 0) fb[s] = (h - 1) / 2 + 1;   // target row r0 = (h - 1) / 2 <= h - 2: rows below it are exact, as all are
+        return;
+    }
+    // what refine_pipe_body sets when a hand-off wait gives up in the first sweep; the sweeps it leaves unfinished are
+    // wiped, so that nothing taken from them can pass for the result
+    if (threadIdx.x == 0) { fb[s] = h - 1; fb[16 + s] = 1; }
+    const long SK = (long)(h + w - 1) * h;
+    for (long q = threadIdx.x; q < SK; q += blockDim.x) { D.rf1[s * SK + q] = -1; D.rf2[s * SK + q] = -1; }
+}
+}  // namespace
+
+extern "C" void r360_refine_force_fallback(uint64_t sensor_mask, int first_sweep) {
+    g_force_fb_mask = sensor_mask;
+    g_force_fb_first = first_sweep;
+}
+
 // refinement mode: -1 the wavefront sweeps (default; pipelined bands for h <= 512), -2 the wavefront sweeps with a
 // barrier per diagonal, 0 the single-wave sweeps, rb > 0 banded with rb rows per band (R360_REFINE_ROWS overrides)
 int refine_band_rows(int h) {
@@ -2323,13 +2421,19 @@ int refine_band_rows(int h) {
 // refine()'s two sweeps over 8 sensors' states (PlaneDev::state, in place) and closeness masks (mask) of each frame of
 // the batch.  rb > 0: banded (phases 1 and 2 per sweep; state2 holds the first sweep's output); rb = 0: one wave per
 // sensor walks every row (k_refine); rb < 0: the wavefront sweeps (rcode / rmsk / rf1 / rf2, rflag).
-int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int h, int rb, bool wave_bufs) {
+// frame: a frame build, which also makes the states and masks from the labels before the sweeps and the refined
+// labels after them; the wavefront path does both inside its skew and unskew passes (k_refine_prep<true>,
+// k_refine_finish), the other paths with k_refine_init / k_refine_final around the sweeps.
+int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int h, int rb, bool wave_bufs, bool frame) {
     const int K = (w + 63) / 64;
     const unsigned nf = (unsigned)F;
+    const int N = w * h;
+    const dim3 px_grid((unsigned)((N + 255) / 256), 8, nf);   // a thread per pixel of a sensor
+    const int blocks = (int)((8L * N + 255) / 256);
     if (rb < 0 && (w < 2 || h > 1024 || !wave_bufs)) rb = 0;
     if (rb < 0) {
-        const long slots = 8L * (h + w - 1) * h;
-        hipLaunchKernelGGL(k_refine_skew, dim3((unsigned)((slots + 255) / 256), 1, nf), dim3(256), 0, st, B, w, h);
+        if (frame) hipLaunchKernelGGL(k_refine_prep<true>, px_grid, dim3(256), 0, st, B, w, h);
+        else hipLaunchKernelGGL(k_refine_prep<false>, px_grid, dim3(256), 0, st, B, w, h);
         const int tpb = 64 * ((h + 63) / 64);
         // a kernel argument kept for the argument layout: always 30 (-1 would take the 64-bit mask path for every sensor)
         const int narrow_max = 30;
@@ -2345,9 +2449,17 @@ int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int 
             hipLaunchKernelGGL(k_refine_wave<1>, dim3(8, 1, nf), dim3(tpb), 0, st, B, w, h);
             hipLaunchKernelGGL(k_refine_wave<-1>, dim3(8, 1, nf), dim3(tpb), 0, st, B, w, h);
         }
-        hipLaunchKernelGGL(k_refine_unskew, dim3((unsigned)((8L * w * h + 255) / 256), 1, nf), dim3(256), 0, st, B, w, h);
+        if (frame && g_force_fb_mask && h >= 2)
+            hipLaunchKernelGGL(k_refine_force_fb, dim3(nf, 8), dim3(256), 0, st, B, w, h, g_force_fb_mask, g_force_fb_first);
+        // the finish first: it leaves alone every sensor k_refine_fb redoes, whose raster states k_refine_fb may still need
+        if (frame) hipLaunchKernelGGL(k_refine_finish, px_grid, dim3(256), 0, st, B, w, h);
+        else hipLaunchKernelGGL(k_refine_unskew, dim3((unsigned)blocks, 1, nf), dim3(256), 0, st, B, w, h);
         switch (K) {
-#define R360_FB_CASE(k) case k: hipLaunchKernelGGL(k_refine_fb<k>, dim3(8, 1, nf), dim3(64), 0, st, B, w, h); break;
+#define R360_FB_CASE(k)                                                                                         \
+    case k:                                                                                                     \
+        if (frame) hipLaunchKernelGGL((k_refine_fb<k, true>), dim3(8, 1, nf), dim3(64), 0, st, B, w, h);        \
+        else hipLaunchKernelGGL((k_refine_fb<k, false>), dim3(8, 1, nf), dim3(64), 0, st, B, w, h);             \
+        break;
             R360_FB_CASE(1) R360_FB_CASE(2) R360_FB_CASE(3) R360_FB_CASE(4) R360_FB_CASE(5)
             R360_FB_CASE(6) R360_FB_CASE(7) R360_FB_CASE(8) R360_FB_CASE(9) R360_FB_CASE(10)
 #undef R360_FB_CASE
@@ -2358,6 +2470,7 @@ int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int 
     }
     if (rb > 0 && (h + rb - 1) / rb > R360_REFINE_BANDS) { r360_set_error("refine: %d rows per band too few", rb); return -2; }
     const int nb = rb > 0 ? (h + rb - 1) / rb : 0;
+    if (frame) hipLaunchKernelGGL(k_refine_init, dim3(blocks, 1, nf), dim3(256), 0, st, B, N);
     switch (K) {
 #define R360_REFINE_CASE(k)                                                                                     \
     case k:                                                                                                     \
@@ -2372,6 +2485,7 @@ int launch_refine_sweeps(const PlaneBatch& B, int F, hipStream_t st, int w, int 
 #undef R360_REFINE_CASE
         default: r360_set_error("refine: cloud width %d > 640 unsupported", w); return -1;
     }
+    if (frame) hipLaunchKernelGGL(k_refine_final, dim3(blocks, 1, nf), dim3(256), 0, st, B, N);
     R360_HIP(hipGetLastError());
     return 0;
 }
@@ -2427,9 +2541,7 @@ int launch_segmentation_geom(const PlaneBatch& B, int F, const PlaneGeom& G, hip
     timing_end(tctx, slot);
     R360_HIP(hipGetLastError());
     slot = timing_begin(tctx, "k_refine");
-    hipLaunchKernelGGL(k_refine_init, dim3(blocks, 1, nf), dim3(256), 0, st, B, N);
-    if (launch_refine_sweeps(B, F, st, w, h, refine_band_rows(h), true)) return -1;
-    hipLaunchKernelGGL(k_refine_final, dim3(blocks, 1, nf), dim3(256), 0, st, B, N);
+    if (launch_refine_sweeps(B, F, st, w, h, refine_band_rows(h), true, true)) return -1;
     timing_end(tctx, slot);
     R360_HIP(hipGetLastError());
     return 0;
@@ -2591,7 +2703,7 @@ extern "C" int r360_refine_eval(const int8_t* state, const uint64_t* mask, int w
     PlaneDev& D = B.f[0];
     D.state = S; D.state2 = S2; D.mask = MK; D.rbnd = bnd; D.rflag = flag;
     D.rcode = code; D.rmsk = msk; D.rf1 = f1; D.rf2 = f2; D.nmodels = nm;
-    int rc = launch_refine_sweeps(B, 1, 0, w, h, rb, true);
+    int rc = launch_refine_sweeps(B, 1, 0, w, h, rb, true, false);
     if (rc == 0) {
         R360_HIP(hipMemcpy(out, S, T, hipMemcpyDeviceToHost));
         if (rb < 0 && w >= 2 && h <= 1024) {
