@@ -26,8 +26,12 @@
 // composed with a fixed wrong transform (0.4 rad about y, (1.0, -0.7, 0.5) m) at J's dense Hessian.  With any of them
 // every optimisation is followed by a "loop edge I J chi2 X weight W" line per loop edge; without them the output is
 // what it was.
+// --clean-map sor:K,MUL[,D] | radius:R,N filters the final map, fused at the optimised poses, where it lies on the GPU
+// (r360::GlobalMap360::removeOutliers: pcl::StatisticalOutlierRemoval with meanK K, multiplier MUL and a search bound of
+// D m, 0.5 by default, or pcl::RadiusOutlierRemoval) and prints one more line, "map cleaned: <before> -> <after> points
+// (<short> short)"; without the flag the output is what it was.
 //   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]
-//                       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J]
+//                       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]
 //          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
 //          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
 #include <rgbd360/rgbd360.h>
@@ -69,8 +73,26 @@ int main(int argc, char** argv) {
     double reject_chi2 = -1.0;                           // --reject-chi2: < 0 = off
     int false_from = -1, false_to = -1;                  // --false-loop
     bool bad_arg = false;
+    bool clean_map = false;                              // --clean-map
+    r360_outlier_params clean;
+    r360_outlier_default_params(&clean);
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
+        if (a == "--clean-map" && k + 1 < argc) {
+            const std::string v = argv[++k];
+            clean_map = true;
+            if (v.compare(0, 4, "sor:") == 0) {
+                clean.kind = R360_OUTLIER_STATISTICAL;
+                const int got = std::sscanf(v.c_str() + 4, "%d,%f,%f", &clean.mean_k, &clean.stddev_mul, &clean.max_dist);
+                bad_arg = bad_arg || got < 2;
+            } else if (v.compare(0, 7, "radius:") == 0) {
+                clean.kind = R360_OUTLIER_RADIUS;
+                bad_arg = bad_arg || std::sscanf(v.c_str() + 7, "%f,%d", &clean.radius, &clean.min_neighbors) != 2;
+            } else {
+                bad_arg = true;
+            }
+            continue;
+        }
         if (a == "--robust" && k + 1 < argc) {
             const std::string v = argv[++k];
             const size_t colon = v.find(':');
@@ -104,13 +126,15 @@ int main(int argc, char** argv) {
     if (bad_arg || (synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
         std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
                              "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n"
-                             "       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J]\n"
+                             "       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]\n"
                              "  --robust       loop edges get the kernel, of width D on sqrt(chi2); chain and PbMap edges stay quadratic\n"
                              "  --reject-chi2  after each optimisation loop edges with chi2 > T are deactivated and the graph is optimised again\n"
                              "  --false-loop   when keyframe J is added, also add a wrong loop edge I -> J (demonstration)\n"
                              "  With any of the three, 'loop edge I J chi2 X weight W' is printed per loop edge after every optimisation\n"
                              "  (--reject-chi2 inf prints and rejects nothing).  The dense Hessians are not calibrated information\n"
-                             "  matrices, so chi2 has no unit scale: choose D and T from these printed values.\n", argv[0]);
+                             "  matrices, so chi2 has no unit scale: choose D and T from these printed values.\n"
+                             "  --clean-map    the final map at the optimised poses through the statistical (sor:meanK,multiplier[,bound in m])\n"
+                             "                 or the radius (radius:R in m,min neighbours) outlier filter, on the GPU\n", argv[0]);
         return 1;
     }
     const bool edge_report = robust_kind != R360_GRAPH_KERNEL_NONE || reject_chi2 >= 0.0 || false_from >= 0;
@@ -378,6 +402,11 @@ int main(int argc, char** argv) {
             sizes[which] = map.size();
         }
         std::printf("global map: %zu points at the chained poses, %zu at the optimised poses\n", sizes[0], sizes[1]);
+        if (clean_map) {   // the map holds the fusion at the optimised poses
+            r360_outlier_stats st;
+            map.removeOutliers(clean, &st);
+            std::printf("map cleaned: %zu -> %zu points (%zu short)\n", sizes[1], map.size(), st.n_short);
+        }
         if (!save.empty()) optimizer.saveGraph(save);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "error: %s\n", e.what());

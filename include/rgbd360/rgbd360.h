@@ -809,8 +809,37 @@ class FilterPointCloud {
         if (rc == 0) cloud.resize(n);
         return rc == 0;
     }
+    // pcl::StatisticalOutlierRemoval (setMeanK, setStddevMulThresh) on the GPU, in place, order kept; a point with fewer
+    // than meanK other points within maxDist is removed and takes no part in the statistics (r360_cloud_filter_outliers)
+    void filterStatistical(PointCloud& cloud, int meanK = 20, float stddevMul = 1.f, float maxDist = 0.5f,
+                           r360_outlier_stats* stats = nullptr) {
+        r360_outlier_params p;
+        r360_outlier_default_params(&p);
+        p.kind = R360_OUTLIER_STATISTICAL;
+        p.mean_k = meanK;
+        p.stddev_mul = stddevMul;
+        p.max_dist = maxDist;
+        filterOutliers(cloud, p, stats, "filterStatistical");
+    }
+    // pcl::RadiusOutlierRemoval (setRadiusSearch, setMinNeighborsInRadius) on the GPU, in place, order kept
+    void filterRadius(PointCloud& cloud, float radius = 0.15f, int minNeighbors = 5, r360_outlier_stats* stats = nullptr) {
+        r360_outlier_params p;
+        r360_outlier_default_params(&p);
+        p.kind = R360_OUTLIER_RADIUS;
+        p.radius = radius;
+        p.min_neighbors = minNeighbors;
+        filterOutliers(cloud, p, stats, "filterRadius");
+    }
     float voxelSize() const { return voxel_; }
   private:
+    void filterOutliers(PointCloud& cloud, const r360_outlier_params& p, r360_outlier_stats* stats, const char* what) {
+        size_t n = 0;
+        Context& c = ctx_ ? *ctx_ : default_context();
+        check(r360_cloud_filter_outliers(c.get(), cloud.xyz.data(), cloud.rgba.data(), cloud.size(), &p, cloud.xyz.data(),
+                                         cloud.rgba.data(), cloud.size(), &n, stats),
+              what);
+        cloud.resize(n);
+    }
     Context* ctx_ = nullptr;
     float voxel_, box_;
 };
@@ -842,6 +871,11 @@ class GlobalMap360 {
         size_t n = size();
         cloud.resize(n);
         check(r360_ctx_map_download(ctx_->get(), cloud.xyz.data(), cloud.rgba.data(), n, &n), "GlobalMap360::download");
+    }
+    // the statistical or the radius outlier filter on the map where it lies (r360_ctx_map_filter_outliers): the map stays
+    // in ascending voxel order and add / size / download go on from the result
+    void removeOutliers(const r360_outlier_params& params, r360_outlier_stats* stats = nullptr) {
+        check(r360_ctx_map_filter_outliers(ctx_->get(), &params, stats), "GlobalMap360::removeOutliers");
     }
   private:
     std::shared_ptr<Context> keep_;

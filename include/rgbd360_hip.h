@@ -736,6 +736,45 @@ int r360_ctx_map_add_frame(r360_ctx* ctx, r360_frame* f, const float pose[16], f
 int r360_ctx_map_size(r360_ctx* ctx, size_t* n);
 int r360_ctx_map_download(r360_ctx* ctx, float* xyz, uint32_t* rgba, size_t cap, size_t* n);
 
+/* ---------------------------------------------------------------- outlier removal
+ * pcl::StatisticalOutlierRemoval and pcl::RadiusOutlierRemoval, restated from PCL 1.7 (unpinned), for a host cloud and
+ * for the context's global map where it lies.  The statement is tests/outlier_model.py and DESIGN.md §5b-2.
+ * Both: a row with a non-finite coordinate is dropped (PCL keeps it as an inlier); kept points keep their input order and
+ * their xyz and rgba bits; the squared distance of two points is dx*dx + dy*dy + dz*dz in double of the float
+ * coordinates, left to right, uncontracted.
+ * STATISTICAL (mean_k = k, stddev_mul, max_dist): d_i = the mean of the square roots of the k smallest squared
+ * distances from point i to other points, summed ascending.  A point whose k-th nearest other point lies farther than
+ * max_dist (squared distance > (double)max_dist squared) is short: removed, and no part of the statistics (PCL
+ * searches without bound; with max_dist beyond the cloud's diameter the two agree).  Over the m other points
+ * mean = sum d / m, stddev = sqrt(sum (d - mean)^2 / (m - 1)) (0 when m < 2), threshold = mean + stddev_mul * stddev;
+ * point i is kept iff d_i <= threshold.
+ * RADIUS (radius, min_neighbors): c_i = the number of other points with squared distance <= (double)radius squared;
+ * point i is kept iff c_i >= min_neighbors (PCL counts the point itself and keeps iff count > min: the same rule).
+ * Defaults: STATISTICAL, mean_k 20, stddev_mul 1, max_dist 0.5 m, radius 0.15 m, min_neighbors 5: ten and three leaves
+ * of the reference's 5 cm voxel, the application's starting values and no claim about any dataset.
+ * Checks (no GPU needed): ctx or params NULL, kind not one of the two, mean_k outside 1..64, max_dist or radius not
+ * positive and finite, stddev_mul not finite, min_neighbors < 0: R360_EINVAL (-2).
+ * stats: n_in rows given, n_finite of them finite, n_short short points, n_removed = n_in - rows kept; mean, stddev and
+ * threshold of the statistical filter (0 for the radius filter, whose n_short is 0 too).
+ * r360_cloud_filter_outliers: rgba, out_rgba and stats may be NULL; the outputs may be the inputs; cap = room in the
+ * outputs: cap < *n_out is an error (< 0) that still sets *n_out.
+ * r360_ctx_map_filter_outliers: the context's map filtered in HBM; only the counts and statistics cross to the host.
+ * The map stays in ascending voxel order, and size, download, add_cloud and add_frame go on from the result.  An empty
+ * map gives 0 and zero stats; an error leaves the map as it was.
+ * r360_cloud_outlier_eval (parity hook): fills the output of the filter named by kind and leaves the other alone:
+ * STATISTICAL score[i] = d_i, +inf for a short point, NaN for a dropped row; RADIUS count[i] = c_i (the full count),
+ * -1 for a dropped row.  Either pointer may be NULL. */
+enum { R360_OUTLIER_STATISTICAL = 0, R360_OUTLIER_RADIUS = 1 };
+typedef struct { int kind; int mean_k; float stddev_mul; float max_dist; float radius; int min_neighbors; } r360_outlier_params;
+typedef struct { size_t n_in, n_finite, n_short, n_removed; double mean, stddev, threshold; } r360_outlier_stats;
+void r360_outlier_default_params(r360_outlier_params* params);
+int r360_cloud_filter_outliers(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n,
+                               const r360_outlier_params* params, float* out_xyz, uint32_t* out_rgba, size_t cap,
+                               size_t* n_out, r360_outlier_stats* stats);
+int r360_ctx_map_filter_outliers(r360_ctx* ctx, const r360_outlier_params* params, r360_outlier_stats* stats);
+int r360_cloud_outlier_eval(r360_ctx* ctx, const float* xyz, size_t n, const r360_outlier_params* params, double* score,
+                            int* count);
+
 /* ---------------------------------------------------------------- Generalized-ICP
  * pcl::GeneralizedIterativeClosestPoint as Registration/RegisterPairRGBD360.cpp:109-149 calls it, restated (PCL is
  * not pinned): the statement is tests/gicp_model.py and DESIGN.md §5c.  Per cloud: rows with a non-finite coordinate

@@ -82,6 +82,44 @@ class GicpStats(C.Structure):
     ]
 
 
+OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1
+
+
+class OutlierParams(C.Structure):
+    """r360_outlier_params — pcl::StatisticalOutlierRemoval (mean_k, stddev_mul, max_dist) or
+    pcl::RadiusOutlierRemoval (radius, min_neighbors), chosen by kind (see include/rgbd360_hip.h)."""
+    _fields_ = [
+        ("kind", C.c_int), ("mean_k", C.c_int), ("stddev_mul", C.c_float), ("max_dist", C.c_float),
+        ("radius", C.c_float), ("min_neighbors", C.c_int),
+    ]
+
+    @classmethod
+    def default(cls) -> "OutlierParams":
+        p = cls()
+        lib().r360_outlier_default_params(C.byref(p))
+        return p
+
+    @classmethod
+    def statistical(cls, mean_k: int = 20, stddev_mul: float = 1.0, max_dist: float = 0.5) -> "OutlierParams":
+        p = cls.default()
+        p.kind, p.mean_k, p.stddev_mul, p.max_dist = OUTLIER_STATISTICAL, mean_k, stddev_mul, max_dist
+        return p
+
+    @classmethod
+    def radius_filter(cls, radius: float = 0.15, min_neighbors: int = 5) -> "OutlierParams":
+        p = cls.default()
+        p.kind, p.radius, p.min_neighbors = OUTLIER_RADIUS, radius, min_neighbors
+        return p
+
+
+class OutlierStats(C.Structure):
+    """r360_outlier_stats — what one outlier filter call saw and did."""
+    _fields_ = [
+        ("n_in", C.c_size_t), ("n_finite", C.c_size_t), ("n_short", C.c_size_t), ("n_removed", C.c_size_t),
+        ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double),
+    ]
+
+
 class GraphParams(C.Structure):
     """r360_graph_params — pose-graph optimisation settings (see include/rgbd360_hip.h)."""
     _fields_ = [
@@ -428,6 +466,11 @@ _SIGS = [
     ("r360_ctx_map_add_frame", C.c_int, [_P, _P, _FP, C.c_float, C.c_float, C.c_float, C.c_float]),
     ("r360_ctx_map_size", C.c_int, [_P, C.POINTER(C.c_size_t)]),
     ("r360_ctx_map_download", C.c_int, [_P, _FP, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_outlier_default_params", None, [C.POINTER(OutlierParams)]),
+    ("r360_cloud_filter_outliers", C.c_int, [_P, _FP, _P, C.c_size_t, C.POINTER(OutlierParams), _FP, _P, C.c_size_t,
+                                             C.POINTER(C.c_size_t), C.POINTER(OutlierStats)]),
+    ("r360_ctx_map_filter_outliers", C.c_int, [_P, C.POINTER(OutlierParams), C.POINTER(OutlierStats)]),
+    ("r360_cloud_outlier_eval", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(OutlierParams), _DP, _IP]),
     ("r360_gicp_default_params", None, [C.POINTER(GicpParams)]),
     ("r360_gicp_set_source", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
     ("r360_gicp_set_target", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
@@ -683,6 +726,41 @@ class Context:
         rgba = np.zeros(n.value, np.uint32)
         _check(lib().r360_ctx_map_download(self.h, _fptr(xyz), _vptr(rgba), n.value, C.byref(n)), "map_download")
         return xyz, rgba
+
+    def filter_outliers(self, xyz, rgba=None, params: "OutlierParams | None" = None):
+        """pcl::StatisticalOutlierRemoval / RadiusOutlierRemoval on this context's GPU (r360_cloud_filter_outliers): the
+        kept points in input order with their bits.  Returns (xyz [m,3], rgba [m] or None, OutlierStats)."""
+        xyz, rgba = _cloud_arrays(xyz, rgba)
+        p = params if params is not None else OutlierParams.default()
+        n = xyz.shape[0]
+        oxyz = np.zeros((n, 3), np.float32)
+        orgba = None if rgba is None else np.zeros(n, np.uint32)
+        m, st = C.c_size_t(), OutlierStats()
+        _check(lib().r360_cloud_filter_outliers(self.h, _fptr(xyz), None if rgba is None else _vptr(rgba), n, C.byref(p),
+                                                _fptr(oxyz), None if rgba is None else _vptr(orgba), n, C.byref(m),
+                                                C.byref(st)), "filter_outliers")
+        return oxyz[:m.value].copy(), None if rgba is None else orgba[:m.value].copy(), st
+
+    def map_filter_outliers(self, params: "OutlierParams | None" = None) -> "OutlierStats":
+        """The same filter on the context's global map where it lies in HBM; only the statistics come back."""
+        p = params if params is not None else OutlierParams.default()
+        st = OutlierStats()
+        _check(lib().r360_ctx_map_filter_outliers(self.h, C.byref(p), C.byref(st)), "map_filter_outliers")
+        return st
+
+    def outlier_eval(self, xyz, params: "OutlierParams"):
+        """Parity hook (r360_cloud_outlier_eval): for a statistical `params` the scores d_i [n] f64 (+inf short, NaN
+        dropped row), for a radius one the full neighbour counts c_i [n] i32 (-1 dropped row)."""
+        xyz, _ = _cloud_arrays(xyz, None)
+        n = xyz.shape[0]
+        if params.kind == OUTLIER_STATISTICAL:
+            out = np.zeros(n, np.float64)
+            _check(lib().r360_cloud_outlier_eval(self.h, _fptr(xyz), n, C.byref(params), _dptr(out), None), "outlier_eval")
+        else:
+            out = np.zeros(n, np.int32)
+            _check(lib().r360_cloud_outlier_eval(self.h, _fptr(xyz), n, C.byref(params), None, out.ctypes.data_as(_IP)),
+                   "outlier_eval")
+        return out
 
     def _gicp_set(self, fn, xyz, params, what):
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)

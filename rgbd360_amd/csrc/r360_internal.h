@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/rgbd360_hip.h"
 #include "host/gicp_host.h"
+#include "host/devmem.h"
 
 #define R360_PI 3.14159265359  // include/Miscellaneous.h:44 (double literal)
 
@@ -359,6 +360,53 @@ int launch_map_finalise(hipStream_t st, const uint4* pts, size_t n, MapCell* tab
                         uint4* out, size_t out_cap);
 int launch_map_unpack(hipStream_t st, const uint4* pts, size_t m, float* xyz, uint32_t* rgba);
 
+// ------------------------------------------------------------------ outlier removal (kernels/outlier_kernels.hip, host/outliers.cpp)
+constexpr size_t R360_OUTLIER_SCAN_BLOCK = 2048;   // values per workgroup of the prefix sums
+constexpr int R360_OUTLIER_MAXB = 256;             // workgroups (= partial records) of the statistics at most
+constexpr int R360_OUTLIER_KMAX = 64;              // mean_k the kNN kernel's LDS columns hold
+// The sparse grid: cell edge ec (at least limit / ring, so a query reads the (2 ring + 1)^3 cells around its own), and
+// the cell one below the lowest occupied one per axis: coordinates relative to it lie in [1, 2^21 - 2].
+struct OutlierGrid { double ec; long long base[3]; int ring; int pad; };
+struct OutlierPartial { double sum; unsigned long long m, n_short, pad; };
+// the small header that crosses to the host: counts, statistics, error bits
+struct OutlierHdr {
+    unsigned long long n_stat, n_short, n_out;
+    double sum, mean, ssq, stddev, threshold;
+    unsigned err, pad;
+};
+// Everything the outlier filters hold on the device, grown on demand and freed with the context.
+struct OutlierState {
+    DevBuf<MapHdr> d_bounds;  PinnedBuf<MapHdr> h_bounds;
+    DevBuf<OutlierHdr> d_hdr; PinnedBuf<OutlierHdr> h_hdr;
+    DevBuf<unsigned long long> keys;     // [table_cap] cell keys, 0 = empty
+    DevBuf<unsigned> cnt, start, fill;   // [table_cap] points per cell, the cell's first point, the scatter's ranks
+    DevBuf<unsigned> pslot;              // [n] the point's cell slot
+    DevBuf<float4> spts;                 // [n_finite] the points in cell order, w = input index (bits)
+    DevBuf<double> score;                // [n] d_i, +inf short, NaN dropped
+    DevBuf<int> count;                   // [n] c_i, -1 dropped
+    DevBuf<unsigned> keep, pos, bsum;    // [n] keep flags and their exclusive prefix; the scans' workgroup sums
+    DevBuf<OutlierPartial> partial;      // [R360_OUTLIER_MAXB]
+    DevBuf<float> up_xyz;                // staging of host arrays
+    DevBuf<uint32_t> up_rgba;
+    DevBuf<uint4> in, out;               // r360_cloud_filter_outliers' packed input and output
+};
+int launch_out_init(hipStream_t st, size_t n, double* score, int* count, unsigned* keep);
+int launch_out_cells(hipStream_t st, const uint4* pts, size_t n, const OutlierGrid& G, unsigned long long* keys,
+                     size_t table_cap, unsigned* cnt, unsigned* pslot, OutlierHdr* hdr);
+int launch_out_scan(hipStream_t st, const unsigned* v, size_t n, unsigned* bsum, unsigned* out, unsigned long long* total);
+int launch_out_scatter(hipStream_t st, const uint4* pts, size_t n, const unsigned* pslot, const unsigned* start,
+                       unsigned* fill, float4* spts, size_t nf, OutlierHdr* hdr);
+int launch_outlier_knn(hipStream_t st, const float4* spts, size_t nf, const OutlierGrid& G, const unsigned long long* keys,
+                       size_t table_cap, const unsigned* start, const unsigned* cnt, double lim2, int k, double* score);
+int launch_outlier_count(hipStream_t st, const float4* spts, size_t nf, const OutlierGrid& G, const unsigned long long* keys,
+                         size_t table_cap, const unsigned* start, const unsigned* cnt, double lim2, int stop, int* count);
+int outlier_sum_blocks(size_t n);
+int launch_out_stats(hipStream_t st, const double* score, size_t n, double mul, OutlierPartial* partial, OutlierHdr* hdr);
+int launch_out_flag_stat(hipStream_t st, const double* score, size_t n, const OutlierHdr* hdr, unsigned* keep);
+int launch_out_flag_radius(hipStream_t st, const int* count, size_t n, int min_neighbors, unsigned* keep);
+int launch_out_compact(hipStream_t st, const uint4* pts, size_t n, const unsigned* keep, const unsigned* pos, uint4* out,
+                       size_t out_cap, OutlierHdr* hdr);
+
 // ------------------------------------------------------------------ Generalized-ICP (kernels/gicp_kernels.hip, host/gicp.cpp)
 // GicpGrid, the uniform grid over a cloud's bounding box, and the host-only logic: host/gicp_host.h
 constexpr int R360_GICP_KMAX = 32;      // k_correspondences the kNN kernel's LDS lists hold
@@ -528,6 +576,7 @@ struct VoxSlot;
 struct r360_ctx {
     MapState vmap;                         // voxel-filter scratch and the context's global map (host/map.cpp)
     GicpState gicp;                        // Generalized-ICP clouds, indices and pass buffers (host/gicp.cpp)
+    OutlierState outl;                     // outlier filters: sparse grid, scores, compaction (host/outliers.cpp)
     TopoState topo;                        // spectral partitioning: matrices, cluster lists, scratch (host/topo.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
