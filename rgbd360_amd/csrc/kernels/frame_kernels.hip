@@ -1,13 +1,13 @@
 // frame_kernels.hip — Frame360 construction on gfx950:
 //   k_undistort : loadDepthEigen + CLAMS undistort           (Frame360.h:254-258, 293-310)
-//   k_stitch(_t): stitchSphericalImage + cvtColor + depth m   (Frame360.h:1099-1148,
-//                 RegisterPhotoICP.h:485-486, 316-317)
+//   k_stitch_t  : stitchSphericalImage + cvtColor + depth m   (Frame360.h:1099-1148,
+//                 RegisterPhotoICP.h:485-486, 316-317), tiled through LDS
 //   k_pyramid   : pyrDown (gray) + buildPyramidRange (depth)  (RegisterPhotoICP.h:292-354)
 //   k_gradient  : calcGradientXY for gray and depth + the alignFrames360 seam mask
 //                 (RegisterPhotoICP.h:365-398, 4538-4549)
 //   k_prep_l0, k_prep_tail : the sphere's pyramid and gradients, the two above tiled through LDS
-// All but the last two are HBM-streaming, one thread per output pixel.  Compiled with -ffp-contract=off so each
-// float expression rounds exactly as the reference's scalar C++ does.
+// k_undistort, k_pyramid and k_gradient are HBM-streaming, one thread per output pixel.  Compiled with
+// -ffp-contract=off so each float expression rounds exactly as the reference's scalar C++ does.
 #include <type_traits>
 #include "../r360_internal.h"
 
@@ -17,7 +17,7 @@ constexpr int TPB = 256;
 
 // ------------------------------------------------------------------ undistort
 __global__ void k_undistort(const uint16_t* __restrict__ depth, float* __restrict__ depth_m, int rows, int cols,
-                            const float* __restrict__ mult, const float* __restrict__ counts, int nx, int bin_w,
+                            const float* __restrict__ mult, const float* __restrict__ counts, int nx, int ny, int bin_w,
                             int bin_h, int nb, double bin_depth, int apply) {
     const long n = (long)R360_NUM_SENSORS * rows * cols;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
@@ -26,7 +26,7 @@ __global__ void k_undistort(const uint16_t* __restrict__ depth, float* __restric
             const int s = (int)(i / ((long)rows * cols));
             const int pix = (int)(i - (long)s * rows * cols);
             const int v = pix / cols, u = pix - v * cols;
-            const long fr = ((long)s * (rows / bin_h) * nx + (long)(v / bin_h) * nx + (u / bin_w)) * nb;
+            const long fr = ((long)s * ny * nx + (long)(v / bin_h) * nx + (u / bin_w)) * nb;   // tables: [8][ny * nx][nb]
             int idx = (int)floor(z / bin_depth);
             idx = idx < nb - 1 ? idx : nb - 1;
             float start = (float)(bin_depth * idx);
@@ -48,10 +48,10 @@ __global__ void k_undistort(const uint16_t* __restrict__ depth, float* __restric
 
 // k_undistort with 4 consecutive pixels of one sensor row per thread (cols % 4 == 0): one 8-byte load and one 16-byte
 // store per thread instead of a 2-byte load and a 4-byte store per pixel, the same per-pixel expressions
-__device__ __forceinline__ float undistort_px(float z, int s, int v, int u, int rows, int cols,
-                                              const float* __restrict__ mult, const float* __restrict__ counts, int nx,
-                                              int bin_w, int bin_h, int nb, double bin_depth) {
-    const long fr = ((long)s * (rows / bin_h) * nx + (long)(v / bin_h) * nx + (u / bin_w)) * nb;
+__device__ __forceinline__ float undistort_px(float z, int s, int v, int u, const float* __restrict__ mult,
+                                              const float* __restrict__ counts, int nx, int ny, int bin_w, int bin_h,
+                                              int nb, double bin_depth) {
+    const long fr = ((long)s * ny * nx + (long)(v / bin_h) * nx + (u / bin_w)) * nb;   // tables: [8][ny * nx][nb]
     int idx = (int)floor(z / bin_depth);
     idx = idx < nb - 1 ? idx : nb - 1;
     float start = (float)(bin_depth * idx);
@@ -66,7 +66,7 @@ __device__ __forceinline__ float undistort_px(float z, int s, int v, int u, int 
 }
 
 __global__ void k_undistort4(const uint16_t* __restrict__ depth, float* __restrict__ depth_m, int rows, int cols,
-                             const float* __restrict__ mult, const float* __restrict__ counts, int nx, int bin_w,
+                             const float* __restrict__ mult, const float* __restrict__ counts, int nx, int ny, int bin_w,
                              int bin_h, int nb, double bin_depth, int apply) {
     const long nq = (long)R360_NUM_SENSORS * rows * cols / 4;
     for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
@@ -83,134 +83,21 @@ __global__ void k_undistort4(const uint16_t* __restrict__ depth, float* __restri
         for (int e = 0; e < 4; ++e) {
             z[e] = (float)dv[e] * 0.001f;                          // convertTo(CV_32FC1, 0.001)
             if (apply && z[e] != 0)                                // discrete_depth_distortion_model.cpp:175-186
-                z[e] = undistort_px(z[e], s, v, u0 + e, rows, cols, mult, counts, nx, bin_w, bin_h, nb, bin_depth);
+                z[e] = undistort_px(z[e], s, v, u0 + e, mult, counts, nx, ny, bin_w, bin_h, nb, bin_depth);
         }
         reinterpret_cast<float4*>(depth_m)[q] = make_float4(z[0], z[1], z[2], z[3]);
     }
 }
 
 // ------------------------------------------------------------------ stitch
-// One thread per sphere pixel.  Sensor k owns columns [(7-k)*rows, (8-k)*rows)  (:1119-1120).
-__global__ void k_stitch(const uint8_t* __restrict__ bgr8, const uint16_t* __restrict__ depth8, int rows, int cols,
-                         int H, int W, const float* __restrict__ sinphi, const float* __restrict__ cosphi,
-                         const float* __restrict__ sinth, const float* __restrict__ costh,
-                         const float* __restrict__ rt_inv, float fx, float fy, float cx, float cy,
-                         uint8_t* __restrict__ sph_bgr, uint16_t* __restrict__ sph_depth, float2* __restrict__ p0,
-                         uint32_t* __restrict__ pk) {
-    const long n = (long)H * W;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const int row = (int)(i / W), col = (int)(i - (long)row * W);
-        const int k = 7 - col / rows;
-        const float* T = rt_inv + 16 * k;
-        const float v0 = sinphi[row], cos_phi = cosphi[row];
-        const float v1 = cos_phi * sinth[col];
-        const float v2 = cos_phi * costh[col];
-        float p0x = T[0] * v0 + T[4] * v1 + T[8] * v2;
-        float p1 = T[1] * v0 + T[5] * v1 + T[9] * v2;
-        float p2 = T[2] * v0 + T[6] * v1 + T[10] * v2;
-        p0x = p0x + T[12]; p1 = p1 + T[13]; p2 = p2 + T[14];
-        const float u = fx * p0x / p2 + cx;                          // :1133
-        const float v = fy * p1 / p2 + cy;                           // :1134
-        uint8_t b = 0, g = 0, r = 0;
-        uint16_t dd = 0;
-        if (u >= 0 && u < cols && v >= 0 && v < rows) {
-            const int iu = (int)u, iv = (int)v;
-            const long si = (long)k * rows * cols + (long)iv * cols + iu;
-            b = bgr8[si * 3 + 0]; g = bgr8[si * 3 + 1]; r = bgr8[si * 3 + 2];
-            const double du = (double)((u - cx) / fx), dv = (double)((v - cy) / fy);
-            dd = (uint16_t)(depth8[si] * sqrt(1 + du * du + dv * dv));  // :1142 (range in mm)
-        }
-        sph_bgr[i * 3 + 0] = b; sph_bgr[i * 3 + 1] = g; sph_bgr[i * 3 + 2] = r;
-        sph_depth[i] = dd;
-        // setSourceFrame / setTargetFrame level 0: CV_RGB2GRAY on BGR data, /255; depth *0.001
-        const int y = (b * 4899 + g * 9617 + r * 1868 + (1 << 13)) >> 14;
-        p0[i] = make_float2((float)y * (float)(1. / 255), (float)dd * 0.001f);
-        if (pk) pk[i] = dd | ((unsigned)y << 16);
-    }
-}
-
-// k_stitch with 4 consecutive sphere pixels of one row per thread (W % 4 == 0): the same per-pixel expressions,
-// with the 4 pixels' BGR bytes, ranges and level-0 {gray, depth} written as 3 + 2 + 8 dwords (byte-granular
-// stores of one pixel per lane were a third of the kernel's memory instructions)
-__global__ void k_stitch4(const uint8_t* __restrict__ bgr8, const uint16_t* __restrict__ depth8, int rows, int cols,
-                          int H, int W, const float* __restrict__ sinphi, const float* __restrict__ cosphi,
-                          const float* __restrict__ sinth, const float* __restrict__ costh,
-                          const float* __restrict__ rt_inv, float fx, float fy, float cx, float cy,
-                          uint8_t* __restrict__ sph_bgr, uint16_t* __restrict__ sph_depth, float2* __restrict__ p0,
-                          uint32_t* __restrict__ pk) {
-    const long nq = (long)H * W / 4;
-    for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-        const long i0 = 4 * q;
-        const int row = (int)(i0 / W), col0 = (int)(i0 - (long)row * W);
-        const float v0 = sinphi[row], cos_phi = cosphi[row];
-        // the four columns' tables as 16-byte loads (col0 % 4 == 0), and the sensor's pose loaded once when the four
-        // pixels share a sensor (every sensor width that is a multiple of 4)
-        const float4 st4 = *reinterpret_cast<const float4*>(sinth + col0);
-        const float4 ct4 = *reinterpret_cast<const float4*>(costh + col0);
-        const float st_[4] = {st4.x, st4.y, st4.z, st4.w}, ct_[4] = {ct4.x, ct4.y, ct4.z, ct4.w};
-        const int kA = 7 - col0 / rows;
-        const bool one_sensor = kA == 7 - (col0 + 3) / rows;
-        const float4* TA4 = reinterpret_cast<const float4*>(rt_inv + 16 * kA);
-        const float4 ta0 = TA4[0], ta1 = TA4[1], ta2 = TA4[2], ta3 = TA4[3];
-        const float TA[16] = {ta0.x, ta0.y, ta0.z, ta0.w, ta1.x, ta1.y, ta1.z, ta1.w,
-                              ta2.x, ta2.y, ta2.z, ta2.w, ta3.x, ta3.y, ta3.z, ta3.w};
-        unsigned char px[12];
-        unsigned short dd4[4];
-        unsigned pk4[4];
-        float2 o[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int col = col0 + e;
-            const int k = 7 - col / rows;
-            float T[16];
-            if (one_sensor) {
-#pragma unroll
-                for (int t = 0; t < 16; ++t) T[t] = TA[t];
-            } else {
-#pragma unroll
-                for (int t = 0; t < 16; ++t) T[t] = rt_inv[16 * k + t];
-            }
-            const float v1 = cos_phi * st_[e];
-            const float v2 = cos_phi * ct_[e];
-            float p0x = T[0] * v0 + T[4] * v1 + T[8] * v2;
-            float p1 = T[1] * v0 + T[5] * v1 + T[9] * v2;
-            float p2 = T[2] * v0 + T[6] * v1 + T[10] * v2;
-            p0x = p0x + T[12]; p1 = p1 + T[13]; p2 = p2 + T[14];
-            const float u = fx * p0x / p2 + cx;                          // :1133
-            const float v = fy * p1 / p2 + cy;                           // :1134
-            uint8_t b = 0, g = 0, r = 0;
-            uint16_t dd = 0;
-            if (u >= 0 && u < cols && v >= 0 && v < rows) {
-                const int iu = (int)u, iv = (int)v;
-                const long si = (long)k * rows * cols + (long)iv * cols + iu;
-                b = bgr8[si * 3 + 0]; g = bgr8[si * 3 + 1]; r = bgr8[si * 3 + 2];
-                const double du = (double)((u - cx) / fx), dv = (double)((v - cy) / fy);
-                dd = (uint16_t)(depth8[si] * sqrt(1 + du * du + dv * dv));  // :1142 (range in mm)
-            }
-            px[3 * e] = b; px[3 * e + 1] = g; px[3 * e + 2] = r;
-            dd4[e] = dd;
-            const int y = (b * 4899 + g * 9617 + r * 1868 + (1 << 13)) >> 14;
-            o[e] = make_float2((float)y * (float)(1. / 255), (float)dd * 0.001f);
-            pk4[e] = dd | ((unsigned)y << 16);
-        }
-        uint3 wb;
-        wb.x = px[0] | (px[1] << 8) | (px[2] << 16) | ((unsigned)px[3] << 24);
-        wb.y = px[4] | (px[5] << 8) | (px[6] << 16) | ((unsigned)px[7] << 24);
-        wb.z = px[8] | (px[9] << 8) | (px[10] << 16) | ((unsigned)px[11] << 24);
-        *reinterpret_cast<uint3*>(sph_bgr + 12 * q) = wb;
-        *reinterpret_cast<uint2*>(sph_depth + i0) = make_uint2(dd4[0] | ((unsigned)dd4[1] << 16),
-                                                                 dd4[2] | ((unsigned)dd4[3] << 16));
-        *reinterpret_cast<float4*>(p0 + i0) = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
-        *reinterpret_cast<float4*>(p0 + i0 + 2) = make_float4(o[2].x, o[2].y, o[3].x, o[3].y);
-        if (pk) *reinterpret_cast<uint4*>(pk + i0) = make_uint4(pk4[0], pk4[1], pk4[2], pk4[3]);
-    }
-}
-
-// k_stitch with the sphere walked in 64-row x 16-column tiles, one wave per sphere column: a sphere column maps onto
-// one sensor row (the sensors are mounted on their side: sphere rows run along sensor columns), so a wave's 64 gathers
-// of BGR bytes and ranges read a few consecutive cache lines of one sensor row, where k_stitch4's row-major waves read
-// 64 sensor rows (a line per byte).  The tile goes through LDS and is stored row-major as k_stitch4 stores it.  Per
-// pixel the expressions of k_stitch (the sensor pose loaded once per column, which is one sensor), bit for bit.
+// Sensor k owns sphere columns [(7-k)*rows, (8-k)*rows)  (:1119-1120).
+// The sphere is walked in 64-row x 16-column tiles, one wave per sphere column: a sphere column maps onto one sensor
+// row (the sensors are mounted on their side: sphere rows run along sensor columns), so a wave's 64 gathers of BGR
+// bytes and ranges read a few consecutive cache lines of one sensor row, where row-major waves read 64 sensor rows (a
+// line per byte).  The tile goes through LDS and is stored row-major, 4 consecutive pixels per thread: their BGR
+// bytes, ranges and level-0 {gray, depth} as 3 + 2 + 8 dwords.  Per pixel the reference's float expressions (the
+// sensor pose loaded once per column, which is one sensor), bit for bit.  The sphere's width is a multiple of the
+// tile's (8 * rows with even sensor rows: r360_calib_create); launch_stitch refuses any other.
 // LEAN: only the packed level-0 image is stored (4 of the 17 bytes per pixel), for frames whose other level-0
 // outputs no kernel reads (frame_level0_lean; the full form runs again if one is asked for, then with pk = null: the
 // packed image stays as it is, saliency flags included).
@@ -668,14 +555,14 @@ int launch_undistort(r360_frame* f) {
     const bool apply = c->has_intrinsics && c->clams.width == f->cols && c->clams.height == f->rows;
     if (f->cols % 4 == 0) {
         hipLaunchKernelGGL(k_undistort4, dim3(grid_for(n / 4)), dim3(TPB), 0, f->ctx->stream, f->d_depth, f->d_depth_m,
-                           f->rows, f->cols, c->clams.d_mult, c->clams.d_counts, c->clams.nx, c->clams.bin_w,
+                           f->rows, f->cols, c->clams.d_mult, c->clams.d_counts, c->clams.nx, c->clams.ny, c->clams.bin_w,
                            c->clams.bin_h, c->clams.num_bins, c->clams.bin_depth, apply ? 1 : 0);
         R360_HIP(hipGetLastError());
         return 0;
     }
     hipLaunchKernelGGL(k_undistort, dim3(grid_for(n)), dim3(TPB), 0, f->ctx->stream, f->d_depth, f->d_depth_m, f->rows,
-                       f->cols, c->clams.d_mult, c->clams.d_counts, c->clams.nx, c->clams.bin_w, c->clams.bin_h,
-                       c->clams.num_bins, c->clams.bin_depth, apply ? 1 : 0);
+                       f->cols, c->clams.d_mult, c->clams.d_counts, c->clams.nx, c->clams.ny, c->clams.bin_w,
+                       c->clams.bin_h, c->clams.num_bins, c->clams.bin_depth, apply ? 1 : 0);
     R360_HIP(hipGetLastError());
     return 0;
 }
@@ -691,35 +578,24 @@ bool frame_level0_lean(const r360_frame* f) {
 
 int launch_stitch(r360_frame* f, bool lean, bool keep_pk) {
     const r360_calib* c = f->calib;
-    const long n = (long)f->sph_rows * f->sph_cols;
-    if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipStreamWaitEvent(f->ctx->stream, e, 0));   // a split upload's BGR copy
-    const int slot = timing_begin(f->ctx, "k_stitch");
-    if (lean && f->sph_cols % STT_C != 0) {
-        r360_set_error("lean stitch: the tiled form only");
+    // the tiled kernel is the only one: 8 * rows with even sensor rows (r360_calib_create) is a multiple of its tile
+    if (f->sph_cols % STT_C != 0) {
+        r360_set_error("stitch: a sphere of %d columns is no multiple of the %d-column tile", f->sph_cols, STT_C);
         return -1;
     }
+    if (hipEvent_t e = f->bgr_wait()) R360_HIP(hipStreamWaitEvent(f->ctx->stream, e, 0));   // a split upload's BGR copy
+    const int slot = timing_begin(f->ctx, "k_stitch");
     // a stitch that writes the packed image writes whole words: the frame has no saliency flags until launch_pyramid
     uint32_t* pk = keep_pk ? nullptr : f->lv[0].pk;
     if (pk) f->sal_int = f->sal_depth = __builtin_nanf("");
-    if (f->sph_cols % STT_C == 0) {
-        const dim3 grid((f->sph_cols / STT_C) * ((f->sph_rows + STT_R - 1) / STT_R));
-        if (lean)
-            hipLaunchKernelGGL(k_stitch_t<true>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
-                               f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
-                               c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
-                               f->d_sph_depth, f->lv[0].p0, pk);
-        else
-            hipLaunchKernelGGL(k_stitch_t<false>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
-                               f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
-                               c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
-                               f->d_sph_depth, f->lv[0].p0, pk);
-    } else if (f->sph_cols % 4 == 0)
-        hipLaunchKernelGGL(k_stitch4, dim3(grid_for(n / 4)), dim3(TPB), 0, f->ctx->stream, f->d_bgr, f->d_depth,
-                           f->rows, f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
+    const dim3 grid((f->sph_cols / STT_C) * ((f->sph_rows + STT_R - 1) / STT_R));
+    if (lean)
+        hipLaunchKernelGGL(k_stitch_t<true>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
+                           f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                            c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
                            f->d_sph_depth, f->lv[0].p0, pk);
     else
-        hipLaunchKernelGGL(k_stitch, dim3(grid_for(n)), dim3(TPB), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
+        hipLaunchKernelGGL(k_stitch_t<false>, grid, dim3(256), 0, f->ctx->stream, f->d_bgr, f->d_depth, f->rows,
                            f->cols, f->sph_rows, f->sph_cols, c->d_st_sinphi, c->d_st_cosphi, c->d_st_sinth,
                            c->d_st_costh, c->d_rt_inv, c->K[0], c->K[4], c->K[6], c->K[7], f->d_sph_bgr,
                            f->d_sph_depth, f->lv[0].p0, pk);

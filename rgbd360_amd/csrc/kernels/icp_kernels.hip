@@ -879,7 +879,7 @@ __device__ __forceinline__ int icp_pass_body(const IcpJobs& jobs, const float* _
         const auto rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(spk), 0, npx * 4, 0x00020000);
         const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(tg), 0, npx * 16, 0x00020000);
         const auto rs_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(J.tpk), 0, npx * 4, 0x00020000);
-        // k_stitch4's expressions; the luma masked to its 8 bits (the saliency flags sit above it)
+        // the stitch's (k_stitch_t's) expressions; the luma masked to its 8 bits (the saliency flags sit above it)
         auto gray_of = [](unsigned v) { return (float)((v >> 16) & 0xffu) * (float)(1. / 255); };
         auto depth_of = [](unsigned v) { return (float)(v & 0xffffu) * 0.001f; };
         auto gG = [&](int t) {

@@ -257,3 +257,172 @@ def span_keys(labels8, keyed8, px=512):
         ok = np.isin(flat[s], np.asarray(sorted(keyed8[s]), np.int64))
         key[s * n:(s + 1) * n] = np.where(ok, s * n + flat[s], -1)
     return [len(set(key[i:i + px].tolist()) - {-1}) for i in range(0, 8 * n, px)]
+
+
+# ------------------------------------------------------------------ frame front end: undistort, stitch, compaction
+# sensor rows x cols of tests/test_gpu_frame_shapes.py -> the pyramid depth the library builds for the sphere they give
+# (W = 8 rows, H = int(W / 6); the stitch walks it in 64-row x 16-column tiles, the compaction in 4096-pixel blocks):
+#   2x2     2x16    one tile with 2 of its 64 rows live, W / 16 == 1
+#   10x14   13x80   odd H, cols % 4 == 2
+#   50x70   66x400  a full tile row plus one of 2 rows; 7 compaction blocks, the last partial; W % 64 != 0: never lean
+#   56x76   74x448  W % 64 == 0 (a setCompaction(False) frame is lean); a partial second tile row; cols % 4 == 0
+#   96x128  128x768 two whole tile rows; lean; exactly 24 compaction blocks; the deepest pyramid
+#   100x134 133x800 three tile rows, the last of 5 rows; odd H
+FRAME_SHAPES = {(2, 2): 1, (10, 14): 1, (50, 70): 2, (56, 76): 2, (96, 128): 6, (100, 134): 1}
+FRAME_LEAN = {(56, 76): True, (96, 128): True, (50, 70): False}
+IDENTITY_RTI = np.tile(np.eye(4, dtype=np.float32).reshape(16), 8)   # the poses a calibration holds before it loads any
+SRC_BLOCK = 4096                       # pixels per block of the source-point compaction
+LIB_PI = 3.14159265359                 # the library's (and the reference's) pi literal
+
+
+def sphere_size(rows):
+    """(H, W) of the sphere stitched from sensors of `rows` rows (Frame360.h:391-392)."""
+    W = 8 * rows
+    return int(W * 0.5 * 60.0 / 180), W
+
+
+def pyramid_depth(R, C, cap=6):
+    """The number of levels the library builds for an R x C sphere: a level needs 2 rows, 8 columns and a width that
+    is a multiple of 4, and an odd level is the last."""
+    n = 0
+    while n < cap:
+        if R < 2 or C < 8 or C % 4:
+            break
+        n += 1
+        if R % 2 or C % 2:
+            break
+        R, C = R // 2, C // 2
+    return n
+
+
+def frame_images(rows, cols, k=0):
+    """8 sensors' BGR in 1..255 and depth in 0..6999 mm with 20 % zeros, seeded from the shape (k: a further set).
+    At 6999 mm the stitch's range, depth * sqrt(1 + du^2 + dv^2), stays far below the 65535 of its uint16 cast."""
+    rng = np.random.default_rng(100000 * rows + 100 * cols + k)
+    b = rng.integers(1, 256, (8, rows, cols, 3), dtype=np.uint8)
+    d = rng.integers(0, 7000, (8, rows, cols)).astype(np.uint16)
+    d[rng.random((8, rows, cols)) < 0.2] = 0
+    return b, d
+
+
+# synthetic CLAMS models: sensor size, bin size in pixels (after the loaders' downsampleParams(2)), frustums per row
+# and column, depth bins and their depth in metres
+CLAMS_CASES = {
+    # cols % 4 == 2: the scalar kernel
+    "50x70": dict(rows=50, cols=70, bin_w=7, bin_h=5, nx=10, ny=10, nb=5, bin_depth=2.0),
+    # k_undistort4 with every quad spanning two frustums
+    "48x64": dict(rows=48, cols=64, bin_w=2, bin_h=6, nx=32, ny=8, nb=5, bin_depth=2.0),
+    # quads that straddle a bin edge at a column that is no multiple of 4 (19, 57); a second table geometry
+    "56x76": dict(rows=56, cols=76, bin_w=19, bin_h=7, nx=4, ny=8, nb=3, bin_depth=1.5),
+    # bins that do not divide the sensor (nx = ceil(70 / 8), ny = ceil(50 / 6), as the reference sizes its grid): the
+    # per-sensor table stride nx * ny is not (rows / bin_h) * nx
+    "50x70_ragged_bins": dict(rows=50, cols=70, bin_w=8, bin_h=6, nx=9, ny=9, nb=5, bin_depth=2.0),
+}
+CLAMS_COUNTS = (0, 49, 50, 51, 1000)   # around the interpolation's `count < 50` test
+CLAMS_EDGE_MM = (0, 1, 999, 1000, 1001, 2000, 8000, 8999, 9000, 9999, 10000, 65535)
+
+
+def clams_tables(name, k):
+    """Sensor k's (counts, multipliers) of a case, each float32 [ny, nx, nb]: another seed per sensor."""
+    c = CLAMS_CASES[name]
+    rng = np.random.default_rng(7000 * c["rows"] + 10 * c["cols"] + 100000 * c["bin_h"] + k)
+    shape = (c["ny"], c["nx"], c["nb"])
+    counts = rng.choice(np.array(CLAMS_COUNTS, np.float32), shape)
+    mult = rng.uniform(0.9, 1.1, shape).astype(np.float32)
+    return counts, mult
+
+
+def write_clams_models(dirpath, name):
+    """The case's eight compact model files (the layout tools/compact_clams.py writes) in dirpath; returns their
+    paths.  The header holds twice the sensor and bin size: both loaders apply downsampleParams(2)."""
+    import os
+    import struct
+    c = CLAMS_CASES[name]
+    paths = []
+    for k in range(8):
+        counts, mult = clams_tables(name, k)
+        p = os.path.join(str(dirpath), f"distortion_model{k + 1}.r360")
+        with open(p, "wb") as f:
+            f.write(b"R360CLAMS1\n")
+            f.write(struct.pack("<iiiiiiid", 2 * c["cols"], 2 * c["rows"], 2 * c["bin_w"], 2 * c["bin_h"], c["nx"],
+                                c["ny"], c["nb"], c["bin_depth"]))
+            f.write(counts.tobytes())
+            f.write(mult.tobytes())
+        paths.append(p)
+    return paths
+
+
+def clams_depth(name):
+    """8 sensors' depth in 0..11999 mm with 10 % zeros; the first pixels of sensor 0 are CLAMS_EDGE_MM."""
+    c = CLAMS_CASES[name]
+    rng = np.random.default_rng(31 * c["rows"] + c["cols"] + 1000 * c["bin_h"])
+    d = rng.integers(0, 12000, (8, c["rows"], c["cols"])).astype(np.uint16)
+    d[rng.random(d.shape) < 0.1] = 0
+    d[0].reshape(-1)[:len(CLAMS_EDGE_MM)] = CLAMS_EDGE_MM
+    return d
+
+
+def clams_branches(name, z, counts):
+    """The branch each pixel of one sensor takes in the undistortion (discrete_depth_distortion_model.cpp:175-186,
+    48-68), restated in numpy: z float32 [rows, cols] in metres, counts [ny, nx, nb].  Boolean masks; `zero`, `idx0_neg`,
+    `idx1_past`, `low_count` and `interpolated` partition the image in the order the code tests them, `past_last_bin`
+    (a depth whose bin index is clamped) lies inside `idx1_past`."""
+    c = CLAMS_CASES[name]
+    nb, bd = c["nb"], c["bin_depth"]
+    v, u = np.mgrid[0:c["rows"], 0:c["cols"]]
+    cnt = counts[v // c["bin_h"], u // c["bin_w"]]                       # [rows, cols, nb]
+    raw = np.floor(z.astype(np.float64) / bd).astype(np.int64)
+    idx = np.minimum(raw, nb - 1)
+    start = (bd * idx).astype(np.float32)
+    idx1 = np.where((z - start).astype(np.float64) < bd / 2, idx, idx + 1)
+    idx0 = idx1 - 1
+    take = lambda i: np.take_along_axis(cnt, np.clip(i, 0, nb - 1)[..., None], axis=2)[..., 0]
+    zero = z == 0
+    idx0_neg = ~zero & (idx0 < 0)
+    idx1_past = ~zero & ~idx0_neg & (idx1 >= nb)
+    rest = ~zero & ~idx0_neg & ~idx1_past
+    low = rest & ((take(idx0) < 50) | (take(idx1) < 50))
+    return dict(zero=zero, idx0_neg=idx0_neg, idx1_past=idx1_past, low_count=low, interpolated=rest & ~low,
+                past_last_bin=~zero & (raw > nb - 1))
+
+
+def src_points_model(lv):
+    """The compacted source points of a pyramid level (the oracle's {gray, depth}) stated in float64: for the pixels
+    with float32(0.3) < d < float32(6.0), in raster order, (gray float32 [n], points float64 [n, 3], d float32 [n]) with
+    the point (d sin phi_r, -d cos phi_r sin theta_c, -d cos phi_r cos theta_c).  phi_r and theta_c are the float32
+    angles the library's tables are built from; their sines and cosines are taken in float64."""
+    d, g = np.asarray(lv["depth"], np.float32), np.asarray(lv["gray"], np.float32)
+    R, C = d.shape
+    ares = np.float32(2 * LIB_PI / C)
+    phi = ((np.float32(0.5 * R - 0.5) - np.arange(R, dtype=np.float32)) * ares).astype(np.float32)
+    theta = (np.arange(C, dtype=np.float32) * ares).astype(np.float32)
+    valid = (d > np.float32(0.3)) & (d < np.float32(6.0))
+    r, c = np.nonzero(valid)
+    dv = d[valid]
+    d64, ph, th = dv.astype(np.float64), phi[r].astype(np.float64), theta[c].astype(np.float64)
+    pts = np.stack([d64 * np.sin(ph), -d64 * np.cos(ph) * np.sin(th), -d64 * np.cos(ph) * np.cos(th)], axis=1)
+    return g[valid], pts, dv
+
+
+SRC_GATE_MM = (0, 299, 300, 301, 5999, 6000, 6001)   # around the strict 0.3 < d < 6.0 gate
+CRAFTED_SPHERES = [(66, 400), (128, 768)]
+CRAFTED_KINDS = ("blocks", "zeros", "gate")
+
+
+def crafted_sphere(rows, cols, kind):
+    """A sphere as images whose ranges are made for the compaction: "blocks": raster pixels 4096..8191 (block 1) all
+    invalid (0, 299 and 6001 mm by turns), 8192..12287 (block 2) all valid, noise elsewhere; "zeros": every range 0;
+    "gate": every range one of SRC_GATE_MM."""
+    rng = np.random.default_rng(17 * rows + cols + len(kind))
+    bgr = rng.integers(0, 256, (rows, cols, 3), dtype=np.uint8)
+    if kind == "zeros":
+        dep = np.zeros((rows, cols), np.uint16)
+    elif kind == "gate":
+        dep = rng.choice(np.array(SRC_GATE_MM, np.uint16), (rows, cols))
+    else:
+        dep = rng.integers(0, 7000, (rows, cols)).astype(np.uint16)
+        dep[rng.random((rows, cols)) < 0.2] = 0
+        flat = dep.reshape(-1)
+        flat[SRC_BLOCK:2 * SRC_BLOCK] = np.resize(np.array([0, 299, 6001], np.uint16), SRC_BLOCK)
+        flat[2 * SRC_BLOCK:3 * SRC_BLOCK] = rng.integers(400, 5900, SRC_BLOCK).astype(np.uint16)
+    return bgr, dep
