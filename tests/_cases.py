@@ -426,3 +426,136 @@ def crafted_sphere(rows, cols, kind):
         flat[SRC_BLOCK:2 * SRC_BLOCK] = np.resize(np.array([0, 299, 6001], np.uint16), SRC_BLOCK)
         flat[2 * SRC_BLOCK:3 * SRC_BLOCK] = rng.integers(400, 5900, SRC_BLOCK).astype(np.uint16)
     return bgr, dep
+
+
+# ------------------------------------------------------------------ per-sensor dense paths: pinhole and rig-frame passes
+# sensor rows x cols of tests/test_gpu_sensor_shapes.py -> the levels of the per-sensor pyramid the library builds
+# (halve while both sizes are even and at least 8, at most SENSOR_MAX_PYR levels); the last level:
+#   2x2     2x2    four pixels, every gradient zero, H = 0
+#   10x14   5x7    both levels below one workgroup, level 1 below one wave: tail pixels only
+#   50x70   25x35  odd in both directions; 3500 px = 4 workgroups, 3.4 strides
+#   56x76   14x19  odd columns only; 28x38: 2 workgroups, 2.08 strides; 14x19 = 266 px: 10 threads pair, the rest tail
+#   96x128  6x8    exactly 4 strides at levels 0 and 1 (pairs only); the last level below one wave; 40 rig-frame jobs
+#   100x134 50x67  odd columns at level 1; 14 workgroups, 3.74 strides
+#   120x160 15x20  odd rows only at the last level; 19 workgroups
+SENSOR_SHAPES = {(2, 2): 1, (10, 14): 2, (50, 70): 2, (56, 76): 3, (96, 128): 5, (100, 134): 2, (120, 160): 4}
+SENSOR_MAX_PYR = 6                     # R360_MAX_PYR
+PASS_TPB, PASS_PPT, PASS_MAX_BLOCKS = 256, 4, 256   # threads per workgroup, pixels per thread, workgroups per job
+SENSOR_CAPTURES = {"dec": 4, "crop": 3}             # the decimated / cropped sample captures -> their level count
+
+
+def sensor_levels(rows, cols, cap=SENSOR_MAX_PYR):
+    """[(rows, cols)] of the per-sensor pyramid of a rows x cols sensor."""
+    out = []
+    while len(out) < cap:
+        out.append((rows, cols))
+        if rows % 2 or cols % 2 or rows < 8 or cols < 8:
+            break
+        rows, cols = rows // 2, cols // 2
+    return out
+
+
+def sensor_images(rows, cols, which):
+    """`noise` images of 8 sensors: BGR uniform, depth uniform in 0..6999 mm with 20 % zeros.  which: "target", "source" or
+    "other" (a third set), each from a seed of its own derived from the shape."""
+    rng = np.random.default_rng(1000003 * rows + 1009 * cols + ("target", "source", "other").index(which))
+    b = rng.integers(0, 256, (8, rows, cols, 3), dtype=np.uint8)
+    d = rng.integers(0, 7000, (8, rows, cols)).astype(np.uint16)
+    d[rng.random((8, rows, cols)) < 0.2] = 0
+    return b, d
+
+
+def sensor_captures(kind, samples_dir):
+    """((target BGR, depth), (source BGR, depth)) of the two QVGA sample captures, "dec": decimated [:, ::2, ::2] to
+    8 x 120 x 160; "crop": cropped [:, 92:148, 122:198] to 8 x 56 x 76."""
+    import os
+    from oracle import oracle360 as O
+    out = []
+    for name in ("sphere_images_1.bin", "sphere_images_10.bin"):
+        b, d = O.load_bin(os.path.join(samples_dir, name))
+        if kind == "dec":
+            b, d = b[:, ::2, ::2], d[:, ::2, ::2]
+        else:
+            b, d = b[:, 92:148, 122:198], d[:, 92:148, 122:198]
+        out.append((np.ascontiguousarray(b), np.ascontiguousarray(d)))
+    return tuple(out)
+
+
+# (translation, rotation) twists: the two of test_gpu_pinhole._poses() and a larger motion, 0.45 rad about y (a shift of
+# 525 tan(0.45) = 254 of the 640 columns' worth of focal length: about 0.4 of the width leaves the image).  No point goes
+# behind the camera: a pixel's ray is at most atan(hypot(320, 240) / 525) = 37.3 degrees off the axis (less on the
+# narrower shapes), the rotation is 26.4 degrees, so Z >= 0.3 cos(63.7 deg) - 0.05 > 0.08 m
+# (tests/test_oracle_sensor_shapes.py checks it on every pixel).
+SENSOR_TWISTS = ([0.01, -0.02, 0.015, 0.01, -0.005, 0.008], [-0.05, 0.03, -0.04, -0.02, 0.03, -0.01],
+                 [0.03, -0.02, 0.04, 0.08, 0.45, -0.06])
+SENSOR_LARGE_POSE = 3                  # index into sensor_poses()
+
+
+def sensor_poses():
+    """The identity, test_gpu_pinhole._poses()'s two twists and the larger motion (true SE(3) exponentials)."""
+    from oracle import oracle360 as O
+    return [np.eye(4, dtype=np.float32)] + [O.exp_se3(t, pseudo=False).astype(np.float32) for t in SENSOR_TWISTS]
+
+
+def pass_blocks(npx):
+    """Workgroups per job of a pinhole or rig-frame pass over npx pixels."""
+    return max(1, min(PASS_MAX_BLOCKS, -(-npx // (PASS_TPB * PASS_PPT))))
+
+
+def pin_thread_classes(npx):
+    """k_pin_pass's loop restated per thread: thread t of the nb * 256 of a job starts at pixel t, takes pixels i and
+    i + stride while i + stride < npx (i += 2 stride), then pixel i alone if i < npx.  Returns the thread counts
+    dict(idle, tail_only, pair_only, pair_and_tail) and the pixels covered (which must be npx)."""
+    stride = pass_blocks(npx) * PASS_TPB
+    out = dict(idle=0, tail_only=0, pair_only=0, pair_and_tail=0)
+    covered = 0
+    for t in range(stride):
+        i, pairs = t, 0
+        while i + stride < npx:
+            pairs += 1
+            i += 2 * stride
+        tail = i < npx
+        covered += 2 * pairs + tail
+        out["pair_and_tail" if pairs and tail else "pair_only" if pairs else "tail_only" if tail else "idle"] += 1
+    return out, covered
+
+
+def _pose_diff(A, B):
+    from oracle import oracle360 as O
+    return O.rot_angle(A[:3, :3], B[:3, :3]), float(np.linalg.norm(A[:3, 3] - B[:3, 3]))
+
+
+_CENSUS = {}
+
+
+def sensor_align_census(kind, method, samples_dir):
+    """The oracle's alignFrames of the 8 sensors of a capture pair from the identity, and each solve's stability: from
+    each of the 12 starts exp(+-1e-7 e_i), i = 1..6, the oracle returns the same rc and a pose within 1e-4 rad and
+    1e-3 m of its unperturbed answer (test_gpu_pinhole._oracle_stable's rule, twelve nudges instead of one).  Per
+    sensor dict(ref=(rc, pose, H, g, stats), stable, drift=(rad, m) the largest over the nudges, derr = the largest
+    change of the final error under them).  Computed once per process and left unchanged."""
+    from oracle import oracle360 as O
+    key = (kind, method)
+    if key in _CENSUS:
+        return _CENSUS[key]
+    (bt, dt), (bs, ds) = sensor_captures(kind, samples_dir)
+    p = O.IcpParams.default(n_pyr=SENSOR_CAPTURES[kind])
+    eye = np.eye(4, dtype=np.float32)
+    out = []
+    for k in range(8):
+        ref = O.align_pinhole(bt[k], dt[k], bs[k], ds[k], init=eye, method=method, params=p)
+        stable, dr_max, dt_max, derr = True, 0.0, 0.0, 0.0
+        for i in range(6):
+            for s in (1e-7, -1e-7):
+                tw = np.zeros(6)
+                tw[i] = s
+                rc, Pp, _, _, stp = O.align_pinhole(bt[k], dt[k], bs[k], ds[k],
+                                                    init=O.exp_se3(tw, pseudo=False).astype(np.float32), method=method,
+                                                    params=p)
+                dr, dtr = _pose_diff(Pp, ref[1])
+                stable = stable and rc == ref[0] and dr <= 1e-4 and dtr <= 1e-3
+                dr_max, dt_max = max(dr_max, dr), max(dt_max, dtr)
+                derr = max(derr, abs(stp.error - ref[4].error))
+        out.append(dict(ref=ref, stable=stable, drift=(dr_max, dt_max), derr=derr))
+    _CENSUS[key] = out
+    return out

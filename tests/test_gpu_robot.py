@@ -72,14 +72,15 @@ def _poses():
             O.exp_se3([0.02, -0.01, 0.03, 0.012, -0.008, 0.01], pseudo=False).astype(np.float32)]
 
 
-def _eval_check(ctx, D, method, levels):
+def _eval_check(ctx, D, method, levels, params=None, poses=None):
+    """params: the library's IcpParams (None: its defaults, 4 levels); poses: None = _poses()."""
     f1, f2 = D["frames"]
     (b1, d1), (b2, d2) = D["raw"]
     reg = R.RegisterRGBD360(ctx)
     for l in levels:
         pyr = [(O.sensor_pyramid(b1[k], d1[k], l + 1)[l], O.sensor_pyramid(b2[k], d2[k], l + 1)[l]) for k in range(8)]
-        for P in _poses():
-            g = reg.eval_dense_robot(f1, f2, l, P, method)
+        for P in (_poses() if poses is None else poses):
+            g = reg.eval_dense_robot(f1, f2, l, P, method, params)
             for k in range(8):
                 trg, src = pyr[k]
                 e, eP, eD, nv, nd = O.error_robot(src, trg, D["rows"], D["cols"], l, P, D["rt"][k], D["rti"][k],
@@ -104,17 +105,20 @@ def test_robot_eval_parity_vga(ctx, vga):
     _eval_check(ctx, vga, R.PHOTO_CONSISTENCY, (0, 3))
 
 
-def _register_check(ctx, D, init, method):
+def _register_check(ctx, D, init, method, params=None):
+    """params: the library's IcpParams (None: its defaults, 4 levels); the oracle runs as many levels."""
     f1, f2 = D["frames"]
     (b1, d1), (b2, d2) = D["raw"]
     reg = R.RegisterRGBD360(ctx)
-    ok = reg.RegisterDensePhotoICP(f1, f2, init, method)
-    ook, opose, oinfo, ost = O.register_dense_robot(b1, d1, b2, d2, D["rt"], D["rti"], init, method)
+    ok = reg.RegisterDensePhotoICP(f1, f2, init, method, params=params)
+    n = 4 if params is None else params.n_pyr
+    ook, opose, oinfo, ost = O.register_dense_robot(b1, d1, b2, d2, D["rt"], D["rti"], init, method,
+                                                    O.IcpParams.default(n_pyr=n))
     st = reg.dense_stats
     assert ok == ook
     assert np.array_equal(reg.getPose(), opose) and np.array_equal(opose, init.astype(np.float32))
-    assert list(st.ran[:4]) == list(ost.ran[:4]) and st.illposed_level == ost.illposed_level
-    for l in range(4):
+    assert list(st.ran[:8]) == list(ost.ran[:8]) and st.illposed_level == ost.illposed_level
+    for l in range(max(4, n)):
         assert np.isclose(st.error[l], ost.error[l], rtol=1e-9, atol=1e-12), l
     if ok:
         sc = max(np.abs(oinfo).max(), 1e-30)
