@@ -134,6 +134,7 @@ def lib() -> C.CDLL:
             "orc_normals": (None, [fp, C.c_int, C.c_int, fp, fp]),
             "orc_segment": (C.c_int, [fp, fp, C.c_int, C.c_int, ip, ip, C.POINTER(Region), C.c_int, ip, C.c_int]),
             "orc_pbmap_build": (vp, [fp, vp, C.c_int, C.c_int, fp]),
+            "orc_pbmap_from_planes": (vp, [C.POINTER(Plane), C.c_int]),
             "orc_pbmap_free": (None, [vp]),
             "orc_pbmap_count": (C.c_int, [vp]),
             "orc_pbmap_get": (C.c_int, [vp, C.c_int, C.POINTER(Plane), fp, C.c_int]),
@@ -551,6 +552,25 @@ class PbMap:
         self.h = lib().orc_pbmap_build(_f(d), _v(b), d.shape[1], d.shape[2], _f(rt))
         if not self.h:
             raise RuntimeError("orc_pbmap_build failed")
+
+    @classmethod
+    def from_planes(cls, planes) -> "PbMap":
+        """A crafted map: dicts with normal, center, d, area, elongation, curvature, nrgb, intensity and optionally
+        ppal, id (default: the position), sensor, n_inliers.  No hull, no moments: for the matcher and the pose."""
+        arr = (Plane * max(1, len(planes)))()
+        for i, (a, p) in enumerate(zip(arr, planes)):
+            a.normal[:] = [float(v) for v in p["normal"]]
+            a.center[:] = [float(v) for v in p["center"]]
+            a.ppal[:] = [float(v) for v in p.get("ppal", (0, 0, 0))]
+            a.nrgb[:] = [float(v) for v in p["nrgb"]]
+            a.d, a.area, a.elongation, a.curvature = p["d"], p["area"], p["elongation"], p["curvature"]
+            a.intensity = p["intensity"]
+            a.id, a.sensor, a.n_inliers = int(p.get("id", i)), int(p.get("sensor", 0)), int(p.get("n_inliers", 1))
+        self = cls.__new__(cls)
+        self.h = lib().orc_pbmap_from_planes(arr, len(planes))
+        if not self.h:
+            raise ValueError("plane ids are not 0..n-1")
+        return self
 
     def __len__(self):
         return lib().orc_pbmap_count(self.h)

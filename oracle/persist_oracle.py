@@ -287,3 +287,33 @@ def pbmap_parse(path: str) -> list[dict]:
                            hull=hull.copy()))
     assert off == len(b), "trailing bytes in PbMap file"
     return planes
+
+
+def pbmap_bytes(planes) -> bytes:
+    """The inverse of pbmap_parse: the R360PBM1 payload (what the gzip container holds) of a list of plane dicts.
+    Keys pbmap_parse returns; the optional ones default to a minimal plane: id = position, sensor 0, ppal 0,
+    moments n_inliers = 1 and zeros, no label, no hull."""
+    out = [b"R360PBM1", struct.pack("<II", 1, len(planes))]
+    for i, p in enumerate(planes):
+        f32 = lambda k, n: [float(np.float32(v)) for v in np.asarray(p[k], np.float32).reshape(n)]  # noqa: E731
+        out.append(struct.pack("<ii", int(p.get("id", i)), int(p.get("sensor", 0))))
+        fl = f32("normal", 3) + f32("center", 3) + (f32("ppal", 3) if "ppal" in p else [0.0] * 3)
+        fl += [float(np.float32(p[k])) for k in ("d", "area", "elongation", "curvature")]
+        fl += f32("nrgb", 3) + [float(np.float32(p["intensity"]))]
+        out.append(struct.pack("<17f", *fl))
+        out.append(struct.pack("<q3q", int(p.get("n_inliers", 1)), *[int(v) for v in p.get("s1", (0, 0, 0))]))
+        out += [int(v).to_bytes(16, "little", signed=True) for v in p.get("s2", (0,) * 6)]
+        out.append(struct.pack("<4q", *[int(v) for v in p.get("c", (0, 0, 0, 0))]))
+        label = p.get("label", "").encode()
+        out.append(struct.pack("<I", len(label)) + label)
+        hull = np.ascontiguousarray(p.get("hull", np.zeros((0, 3))), "<f4").reshape(-1, 3)
+        out.append(struct.pack("<I", len(hull)) + hull.tobytes())
+    return b"".join(out)
+
+
+def pbmap_write(path: str, planes) -> bytes:
+    """pbmap_bytes(planes) in the gzip container loadPbMap reads; returns the payload."""
+    b = pbmap_bytes(planes)
+    with gzip.open(path, "wb") as f:
+        f.write(b)
+    return b

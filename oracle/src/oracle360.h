@@ -201,6 +201,9 @@ void* orc_pbmap_from_segments(int n_sensors, int w, int h, const float* xyz4_all
                               const int* contour_all, const int* contour_base, const float* rt8);
 /* Whole plane half of one frame: depth_m8 = 8 undistorted depth images (metres), bgr8 = 8 BGR. */
 void* orc_pbmap_build(const float* depth_m8, const uint8_t* bgr8, int rows, int cols, const float* rt8);
+/* A PbMap given plane by plane (crafted maps for the matcher tests): descriptors as listed, no hull and no moments.
+ * The matcher indexes planes by id, so ids must be 0..n-1 in order; NULL otherwise. */
+void* orc_pbmap_from_planes(const orc_plane* planes, int n);
 void  orc_pbmap_free(void* h);
 int   orc_pbmap_count(const void* h);
 int   orc_pbmap_get(const void* h, int i, orc_plane* out, float* hull_xyz, int hull_cap);

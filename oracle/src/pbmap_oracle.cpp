@@ -812,6 +812,26 @@ void* orc_pbmap_build(const float* depth_m8, const uint8_t* bgr8, int rows, int 
                                    base, rt8);
 }
 
+void* orc_pbmap_from_planes(const orc_plane* planes, int n) {
+    for (int i = 0; i < n; ++i)
+        if (planes[i].id != i) return nullptr;   // S[sid[i]] below: a plane's id is its position (vPlanes[id])
+    auto* m = new orc_pbmap_s;
+    m->m.planes.resize(size_t(n > 0 ? n : 0));
+    for (int i = 0; i < n; ++i) {
+        const orc_plane& q = planes[i];
+        Plane& p = m->m.planes[size_t(i)];
+        p.normal = {q.normal[0], q.normal[1], q.normal[2]};
+        p.center = {q.center[0], q.center[1], q.center[2]};
+        p.ppal = {q.ppal[0], q.ppal[1], q.ppal[2]};
+        p.d = q.d; p.area = q.area; p.elongation = q.elongation; p.curvature = q.curvature;
+        for (int k = 0; k < 3; ++k) p.nrgb[k] = q.nrgb[k];
+        p.intensity = q.intensity;
+        p.id = q.id; p.sensor = q.sensor;
+        p.st.n = q.n_inliers;
+    }
+    return m;
+}
+
 void orc_pbmap_free(void* h) { delete static_cast<orc_pbmap_s*>(h); }
 
 int orc_pbmap_count(const void* h) { return int(static_cast<const orc_pbmap_s*>(h)->m.planes.size()); }
@@ -903,7 +923,9 @@ int orc_register_pbmap(const void* href, const void* htrg, size_t max_match_plan
         am += S[kv.first].area;                       // SubgraphMatcher::calcAreaMatched
     }
     *area_matched = am;
-    if (int(best.size()) < c.min_planes_recognition) return 0;   // RegisterRGBD360.h:306-310
+    // RegisterRGBD360.h:306: `if (bestMatch.size() < 3)`, a literal; min_planes_recognition is parsed and reported
+    // but does not gate RegisterPbMap
+    if (best.size() < 3) return 0;
     const bool good = consistency(S, T, best, pose, info);
     if (good) {                                                     // :323-334
         float as = 0, at = 0;

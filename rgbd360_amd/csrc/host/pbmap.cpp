@@ -1967,6 +1967,10 @@ extern "C" int r360_frame_load_pbmap(r360_frame* f, const char* path) {
         for (P3& q : p.hull) { in.val(q.x); in.val(q.y); in.val(q.z); }
         if (!in.ok) { delete pm; return fail("truncated"); }
     }
+    // subgraph() returns plane ids and the matcher indexes the plane vector with them (S[si[i]]), as the reference
+    // does with vPlanes[id]: a plane's id is its position
+    for (size_t i = 0; i < pm->planes.size(); ++i)
+        if (pm->planes[i].id != int(i)) { delete pm; return fail("plane ids are not 0..n-1"); }
     gzclose(in.g);
     // like `serialize_planes >> planes`, the loaded map replaces the frame's planes
     planes_join(f);
