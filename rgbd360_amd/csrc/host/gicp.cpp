@@ -1,8 +1,8 @@
 // gicp.cpp — Generalized-ICP on the context's GPU: r360_gicp_set_source / set_target / align and the parity hooks
 // (include/rgbd360_hip.h).  Kernels: kernels/gicp_kernels.hip; the host-only logic (intake, the grid's sizing and
 // build, the 6x6 solve, the inner loop's accept / stop rule): host/gicp_host.h; statement and design: DESIGN.md §5c.
-// Every device buffer is a plain pointer in the r360_ctx's GicpState, grown on demand and freed by
-// r360_ctx_destroy: there is no handle type and no static owner.  Everything runs on the context's stream.
+// Every device buffer is a DevBuf / PinnedBuf member of the r360_ctx's GicpState (devmem.h), grown on demand with a
+// 1024-item floor and freed with the context: there is no handle type and no static owner.  Everything runs on the context's stream.
 #include <cmath>
 #include <cstring>
 
@@ -10,20 +10,7 @@
 
 namespace {
 
-template <class T>
-int regrow(r360_ctx* ctx, T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return 0;
-    if (p) {
-        if (ctx_wait(ctx)) return -1;
-        R360_HIP(hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-    const size_t want = std::max<size_t>(need, 1024);
-    R360_HIP(hipMalloc(&p, sizeof(T) * want));
-    cap = want;
-    return 0;
-}
+size_t floored(size_t need) { return std::max<size_t>(need, 1024); }   // the growth rule of every buffer here
 
 int check_params(const r360_gicp_params* p) {
     CHECK_ARG(p, "null params");
@@ -53,13 +40,13 @@ int set_cloud(r360_ctx* ctx, GicpCloud& C, const float* xyz, size_t n, const r36
     gicp_build_grid(pts, G, sorted, cell_start);
     if (bind_device(ctx->device)) return -1;
     const size_t cells = cell_start.size() - 1;
-    if (regrow(ctx, C.pts, C.cap, m) || regrow(ctx, C.spts, C.spts_cap, m) || regrow(ctx, C.cov6, C.cov_cap, 6 * m) ||
-        regrow(ctx, C.cell_start, C.cells_cap, cells + 1) || regrow(ctx, C.knn, C.knn_cap, m * (size_t)p->k_correspondences))
+    if (C.pts.reserve(ctx, floored(m)) || C.spts.reserve(ctx, floored(m)) || C.cov6.reserve(ctx, floored(6 * m)) ||
+        C.cell_start.reserve(ctx, floored(cells + 1)) || C.knn.reserve(ctx, floored(m * (size_t)p->k_correspondences)))
         return -1;
     hipStream_t st = ctx->stream;
-    R360_HIP(hipMemcpyAsync(C.pts, pts.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(C.spts, sorted.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(C.cell_start, cell_start.data(), sizeof(unsigned) * (cells + 1), hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(C.pts.get(), pts.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(C.spts.get(), sorted.data(), sizeof(float) * 4 * m, hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(C.cell_start.get(), cell_start.data(), sizeof(unsigned) * (cells + 1), hipMemcpyHostToDevice, st));
     C.grid = G;
     C.cells = cells;
     C.k = p->k_correspondences;
@@ -70,20 +57,10 @@ int set_cloud(r360_ctx* ctx, GicpCloud& C, const float* xyz, size_t n, const r36
 
 int ensure_pass_bufs(r360_ctx* ctx) {
     GicpState& S = ctx->gicp;
-    if (S.src.n > S.corr_cap) {
-        if (S.corr_cap && ctx_wait(ctx)) return -1;
-        hipFree(S.corr); hipFree(S.M6); hipFree(S.d2);
-        S.corr = nullptr; S.M6 = nullptr; S.d2 = nullptr; S.corr_cap = 0;
-        const size_t want = std::max<size_t>(S.src.n, 1024);
-        R360_HIP(hipMalloc(&S.corr, sizeof(int) * want));
-        R360_HIP(hipMalloc(&S.M6, sizeof(double) * 6 * want));
-        R360_HIP(hipMalloc(&S.d2, sizeof(double) * want));
-        S.corr_cap = want;
-    }
-    if (!S.partials) R360_HIP(hipMalloc(&S.partials, sizeof(double) * R360_GICP_MAXB * R360_GICP_W));
-    if (!S.d_sums) R360_HIP(hipMalloc(&S.d_sums, sizeof(double) * R360_GICP_W));
-    if (!S.h_sums) R360_HIP(hipHostMalloc(&S.h_sums, sizeof(double) * R360_GICP_W, hipHostMallocDefault));
-    return 0;
+    const size_t want = floored(S.src.n);   // each buffer decides from its own capacity
+    if (S.corr.reserve(ctx, want) || S.M6.reserve(ctx, 6 * want) || S.d2.reserve(ctx, want)) return -1;
+    if (S.partials.reserve(ctx, (size_t)R360_GICP_MAXB * R360_GICP_W) || S.d_sums.reserve(ctx, R360_GICP_W)) return -1;
+    return S.h_sums.reserve(ctx, R360_GICP_W);
 }
 
 int check_ready(r360_ctx* ctx, const r360_gicp_params* p, const float* pose) {
@@ -112,7 +89,7 @@ int corr_pass(r360_ctx* ctx, const double* X, double gate2, int want_m) {
     GicpState& S = ctx->gicp;
     GicpPose P;
     memcpy(P.m, X, sizeof P.m);
-    return launch_gicp_corr(ctx->stream, S.src, S.tgt, P, gate2, want_m, S.corr, S.M6, S.d2);
+    return launch_gicp_corr(ctx->stream, S.src, S.tgt, P, gate2, want_m, S.corr.get(), S.M6.get(), S.d2.get());
 }
 
 // one inner pass at Y: the 29 sums on the host
@@ -120,23 +97,14 @@ int inner_pass(r360_ctx* ctx, const double* Y, double* sums) {
     GicpState& S = ctx->gicp;
     GicpPose P;
     memcpy(P.m, Y, sizeof P.m);
-    if (launch_gicp_pass(ctx->stream, S.src, S.tgt, P, S.corr, S.M6, S.partials, S.d_sums)) return -1;
-    R360_HIP(hipMemcpyAsync(S.h_sums, S.d_sums, sizeof(double) * R360_GICP_W, hipMemcpyDeviceToHost, ctx->stream));
+    if (launch_gicp_pass(ctx->stream, S.src, S.tgt, P, S.corr.get(), S.M6.get(), S.partials.get(), S.d_sums.get())) return -1;
+    R360_HIP(hipMemcpyAsync(S.h_sums.get(), S.d_sums.get(), sizeof(double) * R360_GICP_W, hipMemcpyDeviceToHost, ctx->stream));
     if (ctx_wait(ctx)) return -1;
-    memcpy(sums, S.h_sums, sizeof(double) * R360_GICP_W);
+    memcpy(sums, S.h_sums.get(), sizeof(double) * R360_GICP_W);
     return 0;
 }
 
 }  // namespace
-
-void gicp_state_free(GicpState& S) {
-    for (GicpCloud* C : {&S.src, &S.tgt}) {
-        hipFree(C->pts); hipFree(C->spts); hipFree(C->cell_start); hipFree(C->cov6); hipFree(C->knn);
-    }
-    hipFree(S.corr); hipFree(S.M6); hipFree(S.d2); hipFree(S.partials); hipFree(S.d_sums);
-    hipHostFree(S.h_sums);
-    S = GicpState();
-}
 
 extern "C" void r360_gicp_default_params(r360_gicp_params* p) {
     if (!p) return;
@@ -198,10 +166,10 @@ extern "C" int r360_gicp_align(r360_ctx* ctx, const float init[16], const r360_g
     pose_out_f(X, pose_out);
     // getFitnessScore: every source point's nearest target at the final pose, no range limit
     if (corr_pass(ctx, X, INFINITY, 0)) return -1;
-    if (launch_gicp_sum(ctx->stream, S.d2, S.src.n, S.partials, S.d_sums)) return -1;
-    R360_HIP(hipMemcpyAsync(S.h_sums, S.d_sums, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (launch_gicp_sum(ctx->stream, S.d2.get(), S.src.n, S.partials.get(), S.d_sums.get())) return -1;
+    R360_HIP(hipMemcpyAsync(S.h_sums.get(), S.d_sums.get(), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (ctx_wait(ctx)) return -1;
-    st.fitness = S.h_sums[0] / (double)S.src.n;
+    st.fitness = S.h_sums.get()[0] / (double)S.src.n;
     if (stats) *stats = st;
     return status;
 }
@@ -216,15 +184,15 @@ extern "C" int r360_gicp_get_cloud(r360_ctx* ctx, int which, float* xyz, float* 
     if (ctx_wait(ctx)) return -1;
     if (xyz) {
         std::vector<float> p4(4 * C.n);
-        R360_HIP(hipMemcpy(p4.data(), C.pts, sizeof(float) * 4 * C.n, hipMemcpyDeviceToHost));
+        R360_HIP(hipMemcpy(p4.data(), C.pts.get(), sizeof(float) * 4 * C.n, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < C.n; ++i) memcpy(xyz + 3 * i, &p4[4 * i], 12);
     }
     if (cov6) {   // held in double on the device: M_i inverts a sum whose smallest eigenvalue is 2e-3
         std::vector<double> c(6 * C.n);
-        R360_HIP(hipMemcpy(c.data(), C.cov6, sizeof(double) * 6 * C.n, hipMemcpyDeviceToHost));
+        R360_HIP(hipMemcpy(c.data(), C.cov6.get(), sizeof(double) * 6 * C.n, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < 6 * C.n; ++i) cov6[i] = (float)c[i];
     }
-    if (knn) R360_HIP(hipMemcpy(knn, C.knn, sizeof(int) * C.n * (size_t)C.k, hipMemcpyDeviceToHost));
+    if (knn) R360_HIP(hipMemcpy(knn, C.knn.get(), sizeof(int) * C.n * (size_t)C.k, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -238,7 +206,7 @@ extern "C" int r360_gicp_eval(r360_ctx* ctx, const float pose[16], const r360_gi
     pose_in(pose, X);
     if (corr_pass(ctx, X, gate2_of(p), 1)) return -1;
     if (inner_pass(ctx, X, sums)) return -1;
-    if (corr) R360_HIP(hipMemcpy(corr, S.corr, sizeof(int) * S.src.n, hipMemcpyDeviceToHost));
+    if (corr) R360_HIP(hipMemcpy(corr, S.corr.get(), sizeof(int) * S.src.n, hipMemcpyDeviceToHost));
     if (cost) *cost = sums[0];
     if (g) memcpy(g, sums + 1, sizeof(double) * 6);
     if (H) gicp_unpack_H(sums, H);

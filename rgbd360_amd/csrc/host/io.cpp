@@ -180,8 +180,8 @@ static int sphere_cloud_from_device(r360_frame* f, SphereCloudHost& sc) {
     const size_t per = (size_t)P.w * P.h, n = 8 * per;
     std::vector<float4> xyz(n);
     std::vector<uchar4> rgb(n);
-    R360_HIP(hipMemcpyAsync(xyz.data(), P.cloud, sizeof(float4) * n, hipMemcpyDeviceToHost, f->ctx->stream));
-    R360_HIP(hipMemcpyAsync(rgb.data(), P.rgb, sizeof(uchar4) * n, hipMemcpyDeviceToHost, f->ctx->stream));
+    R360_HIP(hipMemcpyAsync(xyz.data(), P.v.cloud, sizeof(float4) * n, hipMemcpyDeviceToHost, f->ctx->stream));
+    R360_HIP(hipMemcpyAsync(rgb.data(), P.v.rgb, sizeof(uchar4) * n, hipMemcpyDeviceToHost, f->ctx->stream));
     R360_HIP(hipStreamSynchronize(f->ctx->stream));
     sc.width = 8 * P.h;
     sc.height = P.w;

@@ -1,8 +1,8 @@
 // map.cpp — FilterPointCloud::filterVoxel (pcl::VoxelGrid restated from PCL 1.7, unpinned) on the GPU and the
 // context's global map: globalMap += cloud; filter.filterVoxel(globalMap) of SLAM/SphereGraphSLAM.cpp:136-137,
 // :208-209 with the map resident in HBM.  Kernels: kernels/map_kernels.hip; semantics, the quantum and the supported
-// domain: DESIGN.md §5b.  Every device buffer here is a plain pointer in the r360_ctx's MapState, grown on demand
-// and freed by r360_ctx_destroy: there is no handle type and no static owner.
+// domain: DESIGN.md §5b.  Every device buffer here is a DevBuf / PinnedBuf member of the r360_ctx's MapState (devmem.h),
+// grown on demand by the arithmetic below and freed with the context: there is no handle type and no static owner.
 #include <cmath>
 #include <cstring>
 
@@ -10,35 +10,20 @@
 
 namespace {
 
-// frees `p` (after the stream has drained, so no enqueued pass still uses it) and allocates `need` items
-template <class T>
-int regrow(r360_ctx* ctx, T*& p, size_t& cap, size_t need, bool zero, bool geometric = true) {
-    if (need <= cap) return 0;
-    size_t want = std::max<size_t>(need, 1024);
-    // geometric: a growing map does not reallocate per frame
-    if (geometric && cap && want < cap + cap / 2) want = cap + cap / 2;
-    if (p) {
-        if (ctx_wait(ctx)) return -1;
-        R360_HIP(hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-    R360_HIP(hipMalloc(&p, sizeof(T) * want));
-    if (zero) R360_HIP(hipMemsetAsync(p, 0, sizeof(T) * want, ctx->stream));
-    cap = want;
-    return 0;
+// what a buffer of `cap` items grows to for `need`: a 1024-item floor, and half as much again, so that a growing map
+// does not reallocate per frame
+size_t stepped(size_t cap, size_t need) {
+    return need <= cap ? cap : std::max(std::max<size_t>(need, 1024), cap + cap / 2);
 }
 
 int ensure_hdr(r360_ctx* ctx) {
     MapState& M = ctx->vmap;
-    if (!M.d_hdr) R360_HIP(hipMalloc(&M.d_hdr, sizeof(MapHdr)));
-    if (!M.h_hdr) R360_HIP(hipHostMalloc(&M.h_hdr, sizeof(MapHdr), hipHostMallocDefault));
-    return 0;
+    return M.d_hdr.reserve(ctx, 1) || M.h_hdr.reserve(ctx, 1) ? -1 : 0;
 }
 
 int read_hdr(r360_ctx* ctx) {
     MapState& M = ctx->vmap;
-    R360_HIP(hipMemcpyAsync(M.h_hdr, M.d_hdr, sizeof(MapHdr), hipMemcpyDeviceToHost, ctx->stream));
+    R360_HIP(hipMemcpyAsync(M.h_hdr.get(), M.d_hdr.get(), sizeof(MapHdr), hipMemcpyDeviceToHost, ctx->stream));
     return ctx_wait(ctx);
 }
 
@@ -57,12 +42,13 @@ int voxel_run(r360_ctx* ctx, const uint4* pts, size_t n, float leaf, uint4* out,
     *m = 0;
     const float inv = 1.0f / leaf;
     if (ensure_hdr(ctx)) return -1;
-    if (launch_map_bounds(st, pts, n, M.d_hdr)) return -1;
+    if (launch_map_bounds(st, pts, n, M.d_hdr.get())) return -1;
     if (read_hdr(ctx)) return -1;
-    const unsigned long long count = M.h_hdr->count;
+    const MapHdr& H = *M.h_hdr.get();
+    const unsigned long long count = H.count;
     if (count == 0) return 0;
     float mn[3], mx[3];
-    for (int k = 0; k < 3; ++k) { mn[k] = ord2f(M.h_hdr->mn[k]); mx[k] = ord2f(M.h_hdr->mx[k]); }
+    for (int k = 0; k < 3; ++k) { mn[k] = ord2f(H.mn[k]); mx[k] = ord2f(H.mx[k]); }
     // PCL 1.7 voxel_grid.hpp: dx = (int64)((max - min) * inv) + 1 per axis in float; dx*dy*dz > INT32_MAX -> refuse
     __int128 cells_est = 1;
     for (int k = 0; k < 3; ++k) {
@@ -104,26 +90,26 @@ int voxel_run(r360_ctx* ctx, const uint4* pts, size_t n, float leaf, uint4* out,
     size_t cap = 1024;
     while (cap < 2 * occupied_max) cap <<= 1;
     // the table's size stays a power of two (the probe mask), and it is zero whenever no call is running
-    if (regrow(ctx, M.table, M.table_cap, cap, true, false) || regrow(ctx, M.list, M.list_cap, M.table_cap / 2, false, false))
-        return -1;
+    if (M.table.reserve_zeroed(ctx, cap, st) || M.list.reserve(ctx, std::max<size_t>(M.table.cap() / 2, 1024))) return -1;
     const size_t nwords = (cells + 31) / 32, nb = (nwords + R360_MAP_SCAN_BLOCK - 1) / R360_MAP_SCAN_BLOCK;
-    if (regrow(ctx, M.bitmap, M.bitmap_cap, nwords, false) || regrow(ctx, M.wprefix, M.wprefix_cap, nwords, false) ||
-        regrow(ctx, M.bsum, M.bsum_cap, nb, false))
+    if (M.bitmap.reserve(ctx, stepped(M.bitmap.cap(), nwords)) || M.wprefix.reserve(ctx, stepped(M.wprefix.cap(), nwords)) ||
+        M.bsum.reserve(ctx, stepped(M.bsum.cap(), nb)))
         return -1;
-    R360_HIP(hipMemsetAsync(M.bitmap, 0, sizeof(unsigned) * nwords, st));
-    if (launch_map_insert(st, pts, n, G, M.table, M.table_cap, M.bitmap, M.list, M.d_hdr)) return -1;
-    if (launch_map_scan(st, M.bitmap, nwords, M.bsum, M.wprefix)) return -1;
-    if (launch_map_finalise(st, pts, n, M.table, M.table_cap, M.list, M.bitmap, nwords, M.wprefix, M.d_hdr, out, out_cap))
+    R360_HIP(hipMemsetAsync(M.bitmap.get(), 0, sizeof(unsigned) * nwords, st));
+    if (launch_map_insert(st, pts, n, G, M.table.get(), M.table.cap(), M.bitmap.get(), M.list.get(), M.d_hdr.get())) return -1;
+    if (launch_map_scan(st, M.bitmap.get(), nwords, M.bsum.get(), M.wprefix.get())) return -1;
+    if (launch_map_finalise(st, pts, n, M.table.get(), M.table.cap(), M.list.get(), M.bitmap.get(), nwords, M.wprefix.get(),
+                            M.d_hdr.get(), out, out_cap))
         return -1;
     if (read_hdr(ctx)) return -1;
-    if (M.h_hdr->err || M.h_hdr->m > occupied_max) {
+    if (H.err || H.m > occupied_max) {
         // cannot happen with a table at most half full; leave a clean table behind all the same
-        hipMemsetAsync(M.table, 0, sizeof(MapCell) * M.table_cap, st);
+        hipMemsetAsync(M.table.get(), 0, sizeof(MapCell) * M.table.cap(), st);
         ctx_wait(ctx);
-        r360_set_error("voxel grid: internal error (flags %u, %u voxels)", M.h_hdr->err, M.h_hdr->m);
+        r360_set_error("voxel grid: internal error (flags %u, %u voxels)", H.err, H.m);
         return -1;
     }
-    *m = M.h_hdr->m;
+    *m = H.m;
     return 0;
 }
 
@@ -140,20 +126,20 @@ int check_cloud_args(r360_ctx* ctx, const float* xyz, size_t n, float leaf) {
 int upload_cloud(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n, uint4* dst) {
     MapState& M = ctx->vmap;
     if (n == 0) return 0;
-    if (regrow(ctx, M.up_xyz, M.up_xyz_cap, 3 * n, false) || regrow(ctx, M.up_rgba, M.up_rgba_cap, n, false)) return -1;
-    R360_HIP(hipMemcpyAsync(M.up_xyz, xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
-    if (rgba) R360_HIP(hipMemcpyAsync(M.up_rgba, rgba, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    return launch_map_pack_host(ctx->stream, M.up_xyz, rgba ? M.up_rgba : nullptr, n, dst);
+    if (M.up_xyz.reserve(ctx, stepped(M.up_xyz.cap(), 3 * n)) || M.up_rgba.reserve(ctx, stepped(M.up_rgba.cap(), n))) return -1;
+    R360_HIP(hipMemcpyAsync(M.up_xyz.get(), xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
+    if (rgba) R360_HIP(hipMemcpyAsync(M.up_rgba.get(), rgba, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    return launch_map_pack_host(ctx->stream, M.up_xyz.get(), rgba ? M.up_rgba.get() : nullptr, n, dst);
 }
 
 // packed points src[0 .. m) -> host arrays
 int download_cloud(r360_ctx* ctx, const uint4* src, size_t m, float* xyz, uint32_t* rgba) {
     MapState& M = ctx->vmap;
     if (m == 0) return 0;
-    if (regrow(ctx, M.up_xyz, M.up_xyz_cap, 3 * m, false) || regrow(ctx, M.up_rgba, M.up_rgba_cap, m, false)) return -1;
-    if (launch_map_unpack(ctx->stream, src, m, M.up_xyz, M.up_rgba)) return -1;
-    if (xyz) R360_HIP(hipMemcpyAsync(xyz, M.up_xyz, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, ctx->stream));
-    if (rgba) R360_HIP(hipMemcpyAsync(rgba, M.up_rgba, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, ctx->stream));
+    if (M.up_xyz.reserve(ctx, stepped(M.up_xyz.cap(), 3 * m)) || M.up_rgba.reserve(ctx, stepped(M.up_rgba.cap(), m))) return -1;
+    if (launch_map_unpack(ctx->stream, src, m, M.up_xyz.get(), M.up_rgba.get())) return -1;
+    if (xyz) R360_HIP(hipMemcpyAsync(xyz, M.up_xyz.get(), sizeof(float) * 3 * m, hipMemcpyDeviceToHost, ctx->stream));
+    if (rgba) R360_HIP(hipMemcpyAsync(rgba, M.up_rgba.get(), sizeof(uint32_t) * m, hipMemcpyDeviceToHost, ctx->stream));
     return ctx_wait(ctx);
 }
 
@@ -161,27 +147,24 @@ int download_cloud(r360_ctx* ctx, const uint4* src, size_t m, float* xyz, uint32
 int map_reserve(r360_ctx* ctx, size_t extra) {
     MapState& M = ctx->vmap;
     const size_t need = M.map_n + extra;
-    if (need > M.map_cap[M.cur]) {
-        const size_t want = std::max<size_t>(std::max<size_t>(need, 1024), M.map_cap[M.cur] + M.map_cap[M.cur] / 2);
-        uint4* p = nullptr;
-        R360_HIP(hipMalloc(&p, sizeof(uint4) * want));
-        if (M.map_n) {
-            const hipError_t e = hipMemcpyAsync(p, M.map[M.cur], sizeof(uint4) * M.map_n, hipMemcpyDeviceToDevice, ctx->stream);
-            if (e != hipSuccess) { hipFree(p); r360_set_error("map copy -> %s", hipGetErrorString(e)); return -1; }
-        }
-        if (ctx_wait(ctx)) { hipFree(p); return -1; }
-        if (M.map[M.cur]) hipFree(M.map[M.cur]);
-        M.map[M.cur] = p;
-        M.map_cap[M.cur] = want;
+    DevBuf<uint4>& cur = M.map[M.cur];
+    if (need > cur.cap()) {   // a fresh buffer, the map copied into it on the stream, then it takes the old one's place
+        DevBuf<uint4> grown;
+        if (grown.reserve(nullptr, stepped(cur.cap(), need))) return -1;
+        if (M.map_n)
+            R360_HIP(hipMemcpyAsync(grown.get(), cur.get(), sizeof(uint4) * M.map_n, hipMemcpyDeviceToDevice, ctx->stream));
+        if (ctx_wait(ctx)) return -1;
+        cur = std::move(grown);
     }
-    return regrow(ctx, M.map[1 - M.cur], M.map_cap[1 - M.cur], need, false);
+    DevBuf<uint4>& other = M.map[1 - M.cur];
+    return other.reserve(ctx, stepped(other.cap(), need));
 }
 
 // map <- voxel(map ++ the `extra` points already packed behind it)
 int map_commit(r360_ctx* ctx, size_t extra, float leaf) {
     MapState& M = ctx->vmap;
     size_t m = 0;
-    const int rc = voxel_run(ctx, M.map[M.cur], M.map_n + extra, leaf, M.map[1 - M.cur], M.map_cap[1 - M.cur], &m);
+    const int rc = voxel_run(ctx, M.map[M.cur].get(), M.map_n + extra, leaf, M.map[1 - M.cur].get(), M.map[1 - M.cur].cap(), &m);
     if (rc != 0) return rc;   // the guard's soft failure and errors leave the map as it was
     M.cur = 1 - M.cur;
     M.map_n = m;
@@ -189,14 +172,6 @@ int map_commit(r360_ctx* ctx, size_t extra, float leaf) {
 }
 
 }  // namespace
-
-void map_state_free(MapState& M) {
-    hipFree(M.d_hdr); hipHostFree(M.h_hdr);
-    hipFree(M.table); hipFree(M.list); hipFree(M.bitmap); hipFree(M.wprefix); hipFree(M.bsum);
-    hipFree(M.up_xyz); hipFree(M.up_rgba); hipFree(M.in); hipFree(M.out);
-    hipFree(M.map[0]); hipFree(M.map[1]);
-    M = MapState();
-}
 
 extern "C" int r360_cloud_filter_voxel(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n, float leaf,
                                        float* out_xyz, uint32_t* out_rgba, size_t cap, size_t* n_out) {
@@ -206,10 +181,10 @@ extern "C" int r360_cloud_filter_voxel(r360_ctx* ctx, const float* xyz, const ui
     if (n == 0) return 0;
     if (bind_device(ctx->device)) return -1;
     MapState& M = ctx->vmap;
-    if (regrow(ctx, M.in, M.in_cap, n, false) || regrow(ctx, M.out, M.out_cap, n, false)) return -1;
-    if (upload_cloud(ctx, xyz, rgba, n, M.in)) return -1;
+    if (M.in.reserve(ctx, stepped(M.in.cap(), n)) || M.out.reserve(ctx, stepped(M.out.cap(), n))) return -1;
+    if (upload_cloud(ctx, xyz, rgba, n, M.in.get())) return -1;
     size_t m = 0;
-    const int rc = voxel_run(ctx, M.in, n, leaf, M.out, M.out_cap, &m);
+    const int rc = voxel_run(ctx, M.in.get(), n, leaf, M.out.get(), M.out.cap(), &m);
     if (rc < 0) return rc;
     if (rc == 1) {   // PCL: "Leaf size is too small for the input dataset": the output is the input
         *n_out = n;
@@ -220,7 +195,7 @@ extern "C" int r360_cloud_filter_voxel(r360_ctx* ctx, const float* xyz, const ui
     }
     *n_out = m;
     if (cap < m) { r360_set_error("voxel grid: output capacity %zu < %zu voxels", cap, m); return -4; }
-    return download_cloud(ctx, M.out, m, out_xyz, out_rgba);
+    return download_cloud(ctx, M.out.get(), m, out_xyz, out_rgba);
 }
 
 extern "C" int r360_ctx_map_reset(r360_ctx* ctx) {
@@ -242,7 +217,7 @@ extern "C" int r360_ctx_map_add_cloud(r360_ctx* ctx, const float* xyz, const uin
     if (M.map_n + n == 0) return 0;
     if (bind_device(ctx->device)) return -1;
     if (map_reserve(ctx, n)) return -1;
-    if (upload_cloud(ctx, xyz, rgba, n, M.map[M.cur] + M.map_n)) return -1;
+    if (upload_cloud(ctx, xyz, rgba, n, M.map[M.cur].get() + M.map_n)) return -1;
     return map_commit(ctx, n, leaf);
 }
 
@@ -284,7 +259,7 @@ extern "C" int r360_ctx_map_add_frame(r360_ctx* ctx, r360_frame* f, const float 
     if (bind_device(ctx->device)) return -1;
     planes_join(f);   // a plane queue builds the cloud on its own stream: the frame's assembly has waited for it
     const PlaneBufs& P = f->pl;
-    CHECK_ARG(P.cloud && P.rgb && P.w > 0 && P.h > 0, "the frame has no cloud buffers");
+    CHECK_ARG(P.v.cloud && P.v.rgb && P.w > 0 && P.h > 0, "the frame has no cloud buffers");
     const size_t per = (size_t)P.w * P.h, n = 8 * per;
     MapState& M = ctx->vmap;
     CHECK_ARG(M.map_n + n <= (size_t)1 << 30, "more than 2^30 points");
@@ -295,7 +270,8 @@ extern "C" int r360_ctx_map_add_frame(r360_ctx* ctx, r360_frame* f, const float 
     memcpy(rig.rt, f->calib->rt, sizeof rig.rt);
     MapPose T;
     memcpy(T.m, pose, sizeof T.m);
-    if (launch_map_pack_frame(ctx->stream, P.cloud, P.rgb, per, rig, T, x_min, x_max, box, M.map[M.cur] + M.map_n)) return -1;
+    if (launch_map_pack_frame(ctx->stream, P.v.cloud, P.v.rgb, per, rig, T, x_min, x_max, box, M.map[M.cur].get() + M.map_n))
+        return -1;
     return map_commit(ctx, n, leaf);
 }
 
@@ -306,5 +282,5 @@ extern "C" int r360_ctx_map_download(r360_ctx* ctx, float* xyz, uint32_t* rgba, 
     if (M.map_n == 0 || (!xyz && !rgba)) return 0;
     if (cap < M.map_n) { r360_set_error("map download: capacity %zu < %zu points", cap, M.map_n); return -4; }
     if (bind_device(ctx->device)) return -1;
-    return download_cloud(ctx, M.map[M.cur], M.map_n, xyz, rgba);
+    return download_cloud(ctx, M.map[M.cur].get(), M.map_n, xyz, rgba);
 }

@@ -198,16 +198,11 @@ extern "C" int r360_ctx_map_filter_outliers(r360_ctx* ctx, const r360_outlier_pa
     if (M.map_n == 0) return 0;
     if (bind_device(ctx->device)) return -1;
     const int other = 1 - M.cur;
-    if (M.map_cap[other] < M.map_n) {   // the result's buffer: the map's other half, as the voxel step uses it
-        if (ctx_wait(ctx)) return -1;
-        if (M.map[other]) R360_HIP(hipFree(M.map[other]));
-        M.map[other] = nullptr;
-        M.map_cap[other] = 0;
-        R360_HIP(hipMalloc(&M.map[other], sizeof(uint4) * M.map_cap[M.cur]));
-        M.map_cap[other] = M.map_cap[M.cur];
-    }
+    // the result's buffer: the map's other half, as large as the current one, as the voxel step uses it
+    if (M.map[other].cap() < M.map_n && M.map[other].reserve(ctx, M.map[M.cur].cap())) return -1;
     size_t m = 0;
-    if (int rc = outlier_run(ctx, M.map[M.cur], M.map_n, *params, FILTER, M.map[other], M.map_cap[other], &m, stats)) return rc;
+    if (int rc = outlier_run(ctx, M.map[M.cur].get(), M.map_n, *params, FILTER, M.map[other].get(), M.map[other].cap(), &m, stats))
+        return rc;
     M.cur = other;
     M.map_n = m;
     return 0;

@@ -356,77 +356,11 @@ struct LocalPlanesHost {
 };
 
 // ------------------------------------------------------------------ buffers
-int plane_bufs_alloc(r360_frame* f) {
-    PlaneBufs& P = f->pl;
-    if (P.cloud) return 0;
-    P.w = f->cols / 2;
-    P.h = f->rows / 2;
-    const long N = (long)P.w * P.h, T = 8 * N;
-    const long sw = (P.w - 1) / 10 + 5, sh = (P.h - 1) / 10 + 5;
-    P.sd_max = 208;
-    P.grid_cells = sw * sh * P.sd_max;
-    R360_HIP(hipMalloc(&P.cloud, sizeof(float4) * T));
-    R360_HIP(hipMalloc(&P.rgb, sizeof(uchar4) * T));
-    R360_HIP(hipMalloc(&P.nrm, sizeof(float4) * T));
-    R360_HIP(hipMalloc(&P.dist0, sizeof(float) * T));
-    R360_HIP(hipMalloc(&P.dist, sizeof(float) * T));
-    R360_HIP(hipMalloc(&P.grids, sizeof(float2) * 16 * P.grid_cells));
-    R360_HIP(hipMalloc(&P.zmm, sizeof(int) * 16));
-    R360_HIP(hipMalloc(&P.parent, sizeof(int) * T));
-    R360_HIP(hipMalloc(&P.root, sizeof(int) * T));
-    R360_HIP(hipMalloc(&P.lab, sizeof(int) * T));
-    R360_HIP(hipMalloc(&P.labf, sizeof(int) * T));
-    R360_HIP(hipMalloc(&P.cnt, sizeof(int) * T));
-    R360_HIP(hipMalloc(&P.aux, sizeof(int) * 8 * R360_MAX_BIG));
-    R360_HIP(hipMalloc(&P.chunk, sizeof(int) * 8 * ((N + 255) / 256)));
-    R360_HIP(hipMalloc(&P.gpart, sizeof(RegionPart) * R360_GM_COPIES * 8 * R360_MAX_MODELS));
-    R360_HIP(hipMalloc(&P.nlab, sizeof(int) * 8));
-    R360_HIP(hipMalloc(&P.big, sizeof(int) * 8 * R360_MAX_BIG));
-    R360_HIP(hipMalloc(&P.nbig, sizeof(int) * 8));
-    R360_HIP(hipMalloc(&P.mom, sizeof(r360p::Moments) * 8 * R360_MAX_BIG));
-    R360_HIP(hipMalloc(&P.models, sizeof(PlaneModel) * 8 * R360_MAX_MODELS));
-    R360_HIP(hipMalloc(&P.nmodels, sizeof(int) * 8));
-    R360_HIP(hipMalloc(&P.state, T));
-    R360_HIP(hipMalloc(&P.state2, T));
-    R360_HIP(hipMalloc(&P.rbnd, 8L * R360_REFINE_BANDS * P.w));
-    R360_HIP(hipMalloc(&P.rflag, sizeof(int) * 8 * R360_REFINE_BANDS));
-    R360_HIP(hipMalloc(&P.mask, sizeof(unsigned long long) * T));
-    const long SK = 8L * (P.w + P.h - 1) * P.h;
-    R360_HIP(hipMalloc(&P.rcode, sizeof(uint16_t) * SK));
-    R360_HIP(hipMalloc(&P.rmsk, sizeof(unsigned long long) * SK));
-    R360_HIP(hipMalloc(&P.rf1, SK));
-    R360_HIP(hipMalloc(&P.rf2, SK));
-    R360_HIP(hipMalloc(&P.out, sizeof(PlaneOut) * 8 * R360_MAX_MODELS));
-    P.contour_cap = 2 * T;
-    P.vox_cap = T;
-    // the contour and voxel outputs are written by the kernels straight into pinned host memory (a
-    // few hundred KB per frame), so the host assembly needs no second device->host copy
-    R360_HIP(hipHostMalloc(&P.contour, sizeof(float4) * P.contour_cap));
-    R360_HIP(hipMalloc(&P.contour_dev, sizeof(float4) * P.contour_cap));
-    R360_HIP(hipHostMalloc(&P.vox, sizeof(VoxOut) * P.vox_cap));
-    R360_HIP(hipMalloc(&P.vox_dev, sizeof(VoxOut) * P.vox_cap));
-    R360_HIP(hipEventCreateWithFlags(&P.done, hipEventDisableTiming | hipEventBlockingSync));
-    R360_HIP(hipEventCreateWithFlags(&P.ready, hipEventDisableTiming));
-    R360_HIP(hipMalloc(&P.totals, sizeof(long) * 4));
-    R360_HIP(hipMalloc(&P.err, sizeof(int)));
-    R360_HIP(hipHostMalloc(&P.h_out, sizeof(PlaneOut) * 8 * R360_MAX_MODELS));
-    R360_HIP(hipHostMalloc(&P.h_nmodels, sizeof(int) * 16));
-    return 0;
-}
+int plane_bufs_alloc(r360_frame* f) { return f->pl.alloc(f->rows, f->cols); }
 
 void plane_bufs_free(r360_frame* f) {
-    PlaneBufs& P = f->pl;
-    planes_join(f);
-    void* dev[] = {P.cloud, P.rgb, P.nrm, P.dist0, P.dist, P.grids, P.zmm, P.parent, P.root, P.lab, P.labf, P.cnt, P.gpart, P.aux, P.chunk, P.nlab,
-                   P.big, P.nbig, P.mom, P.models, P.nmodels, P.state, P.state2, P.rbnd, P.rflag, P.mask, P.rcode, P.rmsk, P.rf1, P.rf2, P.out, P.totals, P.err, P.vox_dev, P.contour_dev};
-    for (void* p : dev) hipFree(p);
-    hipHostFree(P.contour);
-    hipHostFree(P.vox);
-    hipHostFree(P.h_out);
-    hipHostFree(P.h_nmodels);
-    if (P.done) hipEventDestroy(P.done);
-    if (P.ready) hipEventDestroy(P.ready);
-    P = PlaneBufs();
+    planes_join(f);   // before any memory goes
+    f->pl.release();
     delete f->pbmap;
     f->pbmap = nullptr;
     delete f->local;
@@ -500,18 +434,9 @@ PlaneGeom plane_geom(const r360_frame* f) {
 }
 
 PlaneDev plane_dev(const r360_frame* f, const VoxScratch& vs) {
-    const PlaneBufs& P = f->pl;
-    PlaneDev D;
-    D.depth_m = f->d_depth_m; D.bgr = f->d_bgr;
-    D.cloud = P.cloud; D.rgb = P.rgb; D.nrm = P.nrm; D.dist0 = P.dist0; D.dist = P.dist; D.grids = P.grids; D.zmm = P.zmm;
-    D.parent = P.parent; D.root = P.root; D.lab = P.lab; D.labf = P.labf; D.cnt = P.cnt; D.aux = P.aux; D.chunk = P.chunk;
-    D.nlab = P.nlab; D.big = P.big; D.nbig = P.nbig; D.mom = P.mom; D.models = P.models; D.nmodels = P.nmodels;
-    D.state = P.state; D.state2 = P.state2; D.mask = P.mask; D.rbnd = P.rbnd; D.rflag = P.rflag;
-    D.rcode = P.rcode; D.rmsk = P.rmsk; D.rf1 = P.rf1; D.rf2 = P.rf2;
-    D.out = P.out; D.gpart = P.gpart; D.contour = P.contour; D.contour_dev = P.contour_dev; D.vox = P.vox; D.vox_dev = P.vox_dev; D.totals = P.totals; D.err = P.err;
-    D.h_out = P.h_out; D.h_nmodels = P.h_nmodels; D.rt = f->calib->d_rt;
-    D.vhash = vs.vhash; D.vlist = vs.vlist; D.vcnt = vs.vcnt;
-    D.contour_cap = P.contour_cap; D.vox_cap = P.vox_cap; D.vhash_cap = vs.cap;
+    PlaneDev D = f->pl.v;   // the frame's own buffers; what follows is not the plane half's
+    D.depth_m = f->d_depth_m; D.bgr = f->d_bgr; D.rt = f->calib->d_rt;
+    D.vhash = vs.vhash; D.vlist = vs.vlist; D.vcnt = vs.vcnt; D.vhash_cap = vs.cap;
     return D;
 }
 
@@ -798,7 +723,7 @@ bool asm_dispatch(AsmPool* A, r360_frame* f, int st, const std::string& err) {
         for (int s = 0; s < 8; ++s) {
             order[s] = s;
             wt[s] = 0;
-            for (int m = 0; m < P.h_nmodels[s]; ++m) wt[s] += P.h_out[s * R360_MAX_MODELS + m].hull_n + 32;
+            for (int m = 0; m < P.v.h_nmodels[s]; ++m) wt[s] += P.v.h_out[s * R360_MAX_MODELS + m].hull_n + 32;
         }
         std::stable_sort(order, order + 8, [&](int a, int b) { return wt[a] > wt[b]; });
         for (int s : order) A->ready.push_back({W, s});
@@ -885,7 +810,7 @@ int planes_spawn_assembly(r360_frame* f) {
 // caller's critical path).  Which thread runs a task does not change its result.
 void planes_join(r360_frame* f) {
     PlaneBufs& P = f->pl;
-    if (!P.cloud) return;   // never built planes: nothing was queued
+    if (!P.v.cloud) return;   // never built planes: nothing was queued
     AsmPool& A = asm_pool();
     std::unique_lock<std::mutex> lk(A.m);
     if (f->ctx && f->ctx->join_help) {
@@ -926,8 +851,8 @@ void planes_join(r360_frame* f) {
 // Host part of getPlanes: waits for the assembly thread
 int planes_finish(r360_frame* f) {
     PlaneBufs& P = f->pl;
-    if (!P.cloud && f->pbmap) return 0;   // PbMap loaded from a file (loadPbMap)
-    if (!P.cloud) { r360_set_error("planes were not built (R360_BUILD_PLANES)"); return -2; }
+    if (!P.v.cloud && f->pbmap) return 0;   // PbMap loaded from a file (loadPbMap)
+    if (!P.v.cloud) { r360_set_error("planes were not built (R360_BUILD_PLANES)"); return -2; }
     planes_join(f);
     if (P.worker_rc) { r360_set_error("%s", P.worker_err.c_str()); return P.worker_rc; }
     if (!f->pbmap) { r360_set_error("planes were not built (R360_BUILD_PLANES)"); return -2; }
@@ -947,7 +872,7 @@ double asm_us(std::chrono::steady_clock::time_point a, std::chrono::steady_clock
 
 // the frame's segmentation stayed within the kernels' capacities (else the error, with its code)
 static int planes_capacity_ok(r360_frame* f) {
-    const int err = f->pl.h_nmodels[8];
+    const int err = f->pl.v.h_nmodels[8];
     if (!err) return 0;
     r360_set_error("plane segmentation capacity exceeded (code %d: 1 bilateral depth range, 2 labels, 4 models, "
                    "8 contour length, 16 pools)", err);
@@ -958,8 +883,8 @@ static int planes_capacity_ok(r360_frame* f) {
 static void planes_assemble_sensor(r360_frame* f, int s, std::vector<HPlane>& local, AsmProf* pf) {
     PlaneBufs& P = f->pl;
     static const bool prof = R360_KNOB_STR("R360_PBMAP_PROFILE") != nullptr;
-    const float4* contour = P.contour;
-    const VoxOut* vox = P.vox;
+    const float4* contour = P.v.contour;
+    const VoxOut* vox = P.v.vox;
     static thread_local std::vector<HullPt> hq;
     auto tick = [&](double& acc, std::chrono::steady_clock::time_point& t) {
         if (!prof) return;
@@ -971,8 +896,8 @@ static void planes_assemble_sensor(r360_frame* f, int s, std::vector<HPlane>& lo
     local.clear();
     std::vector<std::vector<int>>* keep = f->local ? &f->local->labels[s] : nullptr;
     if (keep) keep->clear();
-    for (int m = 0; m < P.h_nmodels[s]; ++m) {
-        const PlaneOut& O = P.h_out[s * R360_MAX_MODELS + m];
+    for (int m = 0; m < P.v.h_nmodels[s]; ++m) {
+        const PlaneOut& O = P.v.h_out[s * R360_MAX_MODELS + m];
         HPlane pl;
         pl.sensor = s;
         pl.center = {O.model.centroid[0], O.model.centroid[1], O.model.centroid[2]};
@@ -1092,7 +1017,7 @@ static int planes_assemble_group(r360_frame* f, std::vector<std::vector<HPlane>>
             t.pre += pf[s].pre; t.hull += pf[s].hull; t.desc += pf[s].desc; t.local += pf[s].local;
             t.in += pf[s].in; t.kept += pf[s].kept; t.hullv += pf[s].hullv; t.models += pf[s].models; t.vox += pf[s].vox;
         }
-        const long* totals = reinterpret_cast<const long*>(f->pl.h_nmodels + 10);
+        const long* totals = reinterpret_cast<const long*>(f->pl.v.h_nmodels + 10);
         fprintf(stderr, "[pbmap] pools %ld+%ld pts (voxel table %ld cells, bound %ld) | sensors %.0f us: prefilter %.0f, "
                 "hull %.0f, area+desc %.0f, local merges %.0f | groupPlanes %.0f us, mergePlanes %.0f us | models %ld, "
                 "points %ld (voxels %ld) -> %ld kept -> %ld hull vertices, planes %zu\n", totals[0], totals[1],
@@ -1691,38 +1616,38 @@ extern "C" int r360_register(r360_ctx* ctx, r360_frame* ref, r360_frame* trg, co
 
 // ------------------------------------------------------------------ inspection (parity tests)
 extern "C" int r360_frame_get_cloud(r360_frame* f, float* xyz4, uint8_t* rgb4, float* nrm4, float* dist) {
-    CHECK_ARG(f && (f->built & R360_BUILD_CLOUD) && f->pl.cloud, "frame cloud not built (R360_BUILD_CLOUD)");
+    CHECK_ARG(f && (f->built & R360_BUILD_CLOUD) && f->pl.v.cloud, "frame cloud not built (R360_BUILD_CLOUD)");
     PlaneBufs& P = f->pl;
     const size_t T = 8 * (size_t)P.w * P.h;
     hipStream_t st = f->ctx->stream;
-    if (xyz4) R360_HIP(hipMemcpyAsync(xyz4, P.cloud, sizeof(float4) * T, hipMemcpyDeviceToHost, st));
-    if (rgb4) R360_HIP(hipMemcpyAsync(rgb4, P.rgb, sizeof(uchar4) * T, hipMemcpyDeviceToHost, st));
-    if (nrm4) R360_HIP(hipMemcpyAsync(nrm4, P.nrm, sizeof(float4) * T, hipMemcpyDeviceToHost, st));
-    if (dist) R360_HIP(hipMemcpyAsync(dist, P.dist, sizeof(float) * T, hipMemcpyDeviceToHost, st));
+    if (xyz4) R360_HIP(hipMemcpyAsync(xyz4, P.v.cloud, sizeof(float4) * T, hipMemcpyDeviceToHost, st));
+    if (rgb4) R360_HIP(hipMemcpyAsync(rgb4, P.v.rgb, sizeof(uchar4) * T, hipMemcpyDeviceToHost, st));
+    if (nrm4) R360_HIP(hipMemcpyAsync(nrm4, P.v.nrm, sizeof(float4) * T, hipMemcpyDeviceToHost, st));
+    if (dist) R360_HIP(hipMemcpyAsync(dist, P.v.dist, sizeof(float) * T, hipMemcpyDeviceToHost, st));
     R360_HIP(hipStreamSynchronize(st));
     return 0;
 }
 
 extern "C" int r360_frame_get_labels(r360_frame* f, int* lab, int* labf) {
-    CHECK_ARG(f && (f->built & R360_BUILD_PLANES) && f->pl.cloud, "frame planes not built (R360_BUILD_PLANES)");
+    CHECK_ARG(f && (f->built & R360_BUILD_PLANES) && f->pl.v.cloud, "frame planes not built (R360_BUILD_PLANES)");
     PlaneBufs& P = f->pl;
     const size_t T = 8 * (size_t)P.w * P.h;
     hipStream_t st = f->ctx->stream;
-    if (lab) R360_HIP(hipMemcpyAsync(lab, P.lab, sizeof(int) * T, hipMemcpyDeviceToHost, st));
-    if (labf) R360_HIP(hipMemcpyAsync(labf, P.labf, sizeof(int) * T, hipMemcpyDeviceToHost, st));
+    if (lab) R360_HIP(hipMemcpyAsync(lab, P.v.lab, sizeof(int) * T, hipMemcpyDeviceToHost, st));
+    if (labf) R360_HIP(hipMemcpyAsync(labf, P.v.labf, sizeof(int) * T, hipMemcpyDeviceToHost, st));
     R360_HIP(hipStreamSynchronize(st));
     return 0;
 }
 
 extern "C" int r360_frame_get_regions(r360_frame* f, int sensor, r360_region* out, int cap, int* n) {
     if (int rc = ready(f)) return rc;
-    CHECK_ARG(f->pl.cloud, "frame planes were loaded, not built: no per-sensor regions");
+    CHECK_ARG(f->pl.v.cloud, "frame planes were loaded, not built: no per-sensor regions");
     CHECK_ARG(sensor >= 0 && sensor < 8, "sensor out of range");
     PlaneBufs& P = f->pl;
-    const int nm = P.h_nmodels[sensor];
+    const int nm = P.v.h_nmodels[sensor];
     if (n) *n = nm;
     for (int m = 0; m < nm && m < cap && out; ++m) {
-        const PlaneOut& O = P.h_out[sensor * R360_MAX_MODELS + m];
+        const PlaneOut& O = P.v.h_out[sensor * R360_MAX_MODELS + m];
         r360_region& r = out[m];
         r.label = O.model.label;
         r.count = (int)O.stats.n;
@@ -1789,8 +1714,8 @@ extern "C" int r360_frames_segment_eval(r360_frame* const* frames, int n, const 
         R360_HIP(hipStreamSynchronize(st));
         f->bgr_split = false;
         R360_HIP(hipMemcpy(f->d_bgr, bgr.data(), bgr.size(), hipMemcpyHostToDevice));
-        R360_HIP(hipMemcpy(P.cloud, fx, sizeof(float4) * T, hipMemcpyHostToDevice));
-        R360_HIP(hipMemcpy(P.nrm, nrm_comps == 3 ? n4.data() : fn, sizeof(float4) * T, hipMemcpyHostToDevice));
+        R360_HIP(hipMemcpy(P.v.cloud, fx, sizeof(float4) * T, hipMemcpyHostToDevice));
+        R360_HIP(hipMemcpy(P.v.nrm, nrm_comps == 3 ? n4.data() : fn, sizeof(float4) * T, hipMemcpyHostToDevice));
         G = plane_geom(f);
         long cells, entries, groups;
         vox_scratch_need(G, &cells, &entries, &groups);
@@ -1818,7 +1743,7 @@ extern "C" int r360_frames_segment_eval(r360_frame* const* frames, int n, const 
         r360_frame* f = frames[i];
         PlaneBufs& P = f->pl;
         f->built = R360_BUILD_CLOUD | R360_BUILD_PLANES;
-        if (err_codes) err_codes[i] = P.h_nmodels[8];
+        if (err_codes) err_codes[i] = P.v.h_nmodels[8];
         if (planes_capacity_ok(f)) {
             P.worker_rc = -1;
             P.worker_err = r360_last_error();
@@ -1844,21 +1769,21 @@ extern "C" int r360_frame_segment_eval(r360_frame* f, const float* xyz4, const f
 extern "C" int r360_frame_get_refine_states(r360_frame* f, int8_t* state, int* flags) {
     CHECK_ARG(state && flags, "get_refine_states: null output");
     if (int rc = ready(f)) return rc;
-    CHECK_ARG(f->pl.cloud, "frame planes were loaded, not built: no refinement states");
+    CHECK_ARG(f->pl.v.cloud, "frame planes were loaded, not built: no refinement states");
     PlaneBufs& P = f->pl;
-    R360_HIP(hipMemcpy(state, P.state, 8 * (size_t)P.w * P.h, hipMemcpyDeviceToHost));
-    R360_HIP(hipMemcpy(flags, P.rflag, sizeof(int) * 24, hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(state, P.v.state, 8 * (size_t)P.w * P.h, hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(flags, P.v.rflag, sizeof(int) * 24, hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int r360_frame_get_region_detail(r360_frame* f, int sensor, int region, int64_t* stats, float* bounds,
                                             float* contour4, int cap, int* n_contour) {
     if (int rc = ready(f)) return rc;
-    CHECK_ARG(f->pl.cloud, "frame planes were loaded, not built: no per-sensor regions");
+    CHECK_ARG(f->pl.v.cloud, "frame planes were loaded, not built: no per-sensor regions");
     CHECK_ARG(sensor >= 0 && sensor < 8, "sensor out of range");
     PlaneBufs& P = f->pl;
-    CHECK_ARG(region >= 0 && region < P.h_nmodels[sensor], "region out of range");
-    const PlaneOut& O = P.h_out[sensor * R360_MAX_MODELS + region];
+    CHECK_ARG(region >= 0 && region < P.v.h_nmodels[sensor], "region out of range");
+    const PlaneOut& O = P.v.h_out[sensor * R360_MAX_MODELS + region];
     if (stats) {
         stats[0] = O.stats.n;
         for (int k = 0; k < 3; ++k) stats[1 + k] = O.stats.s1[k];
@@ -1875,10 +1800,10 @@ extern "C" int r360_frame_get_region_detail(r360_frame* f, int sensor, int regio
     if (n_contour) *n_contour = (int)nc;
     if (contour4 && nc > 0) {
         CHECK_ARG(cap >= nc, "region contour: buffer too small");
-        CHECK_ARG(O.contour_off >= 0 && O.contour_off + nc <= P.contour_cap, "region contour outside the pool");
+        CHECK_ARG(O.contour_off >= 0 && O.contour_off + nc <= P.v.contour_cap, "region contour outside the pool");
         if (bind_device(f->ctx->device)) return -1;
         R360_HIP(hipStreamSynchronize(f->ctx->stream));
-        R360_HIP(hipMemcpy(contour4, P.contour_dev + O.contour_off, sizeof(float4) * nc, hipMemcpyDeviceToHost));
+        R360_HIP(hipMemcpy(contour4, P.v.contour_dev + O.contour_off, sizeof(float4) * nc, hipMemcpyDeviceToHost));
     }
     return 0;
 }

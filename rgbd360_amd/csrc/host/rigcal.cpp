@@ -679,7 +679,7 @@ extern "C" int r360_rigcal_add_frame(r360_rigcal* h, r360_frame* f, const r360_r
         DevBuf<longlong2> d_sums;
         if (d_keys.reserve(ctx, keys.size()) || d_sums.reserve(ctx, keys.size())) return -1;
         int rc = hipMemcpyAsync(d_keys.get(), keys.data(), sizeof(int2) * keys.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess;
-        if (!rc) rc = launch_rigcal_pixsum(ctx->stream, f->pl.labf, f->pl.w, f->pl.h, d_keys.get(), (int)keys.size(), d_sums.get());
+        if (!rc) rc = launch_rigcal_pixsum(ctx->stream, f->pl.v.labf, f->pl.w, f->pl.h, d_keys.get(), (int)keys.size(), d_sums.get());
         if (!rc) rc = hipMemcpyAsync(sums.data(), d_sums.get(), sizeof(longlong2) * keys.size(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess;
         if (!rc) rc = ctx_wait(ctx);
         if (rc) { r360_set_error("rigcal: the pixel sums failed"); return -1; }

@@ -307,9 +307,6 @@ extern "C" void r360_ctx_destroy(r360_ctx* c) {
     hipFree(c->d_match_desc); hipFree(c->d_unary); hipFree(c->d_bin); hipFree(c->d_vhash);
     hipFree(c->d_vlist); hipFree(c->d_vcnt);
     for (auto& s : c->bvox) vox_slot_free(s);
-    map_state_free(c->vmap);   // voxel-filter scratch and the context's global map
-    gicp_state_free(c->gicp);  // Generalized-ICP clouds and pass buffers
-    topo_state_free(c->topo);  // spectral partitioning buffers
     hipHostFree(c->h_unary); hipHostFree(c->h_bin);
     if (c->up_stream) {
         hipStreamSynchronize(c->up_stream);
@@ -392,73 +389,17 @@ static void inverse4(const float* T, float* Ti) {  // rigid-or-general 4x4 inver
     for (int i = 0; i < 16; ++i) Ti[i] = (float)(inv[i] / det);
 }
 
-static int upload_floats(float** dptr, const std::vector<float>& h) {
-    if (*dptr) hipFree(*dptr);
-    R360_HIP(hipMalloc(dptr, sizeof(float) * (h.size() ? h.size() : 1)));
-    R360_HIP(hipMemcpy(*dptr, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
-    return 0;
-}
-
-// Trigonometric tables with the reference's exact float expressions:
-//   stitchImage (Frame360.h:1104-1129) and the alignFrames360 LUT (RegisterPhotoICP.h:4555-4569).
-// sph_rows / sph_cols: the sphere size; 0 = the one stitchSphericalImage produces from the sensors
-// (width 8 * rows, height width / 6, Frame360.h:391-392)
-static int calib_build_tables(r360_calib* c, int sph_rows = 0, int sph_cols = 0) {
-    const int W = sph_cols ? sph_cols : c->rows * 8;
-    const int H = sph_rows ? sph_rows : (int)(W * 0.5 * 60.0 / 180);
-    c->sph_rows = H; c->sph_cols = W;
-    if (c->rows == 0) goto levels;   // sphere-only calibration: no stitch tables
-    {
-    const float offsetPhi = H / 2 - 0.5;
-    const float offsetTheta = -c->rows * 15 / 2 + 0.5;
-    const float angle_pixel = 2 * R360_PI / W;
-    std::vector<float> sp(H), cp(H), st(W), ct(W);
-    for (int r = 0; r < H; ++r) { float phi_i = (offsetPhi - r) * angle_pixel; sp[r] = std::sin(phi_i); cp[r] = std::cos(phi_i); }
-    for (int col = 0; col < W; ++col) { float th = (col + offsetTheta) * angle_pixel; st[col] = std::sin(th); ct[col] = std::cos(th); }
-    if (upload_floats(&c->d_st_sinphi, sp) || upload_floats(&c->d_st_cosphi, cp) ||
-        upload_floats(&c->d_st_sinth, st) || upload_floats(&c->d_st_costh, ct))
-        return -1;
-    }
-levels:
-    // pyramid levels of the sphere
-    int R = H, C = W, nl = 0;
-    for (; nl < R360_MAX_PYR; ++nl) {
-        if (R < 2 || C < 8 || (C % 4) != 0) break;
-        const float angle_res = 2 * R360_PI / C;
-        const float half_nRows = 0.5 * R - 0.5;
-        std::vector<float> a(R), b(R), s(C), t(C);
-        for (int cc = 0; cc < C; ++cc) { float theta = cc * angle_res; s[cc] = std::sin(theta); t[cc] = std::cos(theta); }
-        for (int r = 0; r < R; ++r) { float phi = (half_nRows - r) * angle_res; a[r] = std::sin(phi); b[r] = std::cos(phi); }
-        LevelTrig& L = c->trig[nl];
-        if (upload_floats(&L.sinphi, a) || upload_floats(&L.cosphi, b) || upload_floats(&L.sinth, s) ||
-            upload_floats(&L.costh, t))
-            return -1;
-        if ((R % 2) || (C % 2)) { ++nl; break; }
-        R /= 2; C /= 2;
-    }
-    c->n_levels = nl;
-    return 0;
-}
-
 extern "C" int r360_calib_create(r360_ctx* ctx, int rows, int cols, r360_calib** out) {
     CHECK_ARG(ctx && out, "null arg");
     CHECK_ARG(rows > 0 && cols > 0 && rows % 2 == 0 && cols % 2 == 0, "sensor size must be even");
-    R360_HIP(hipSetDevice(ctx->device));
-    r360_calib* c = new r360_calib;
-    c->ctx = ctx; c->rows = rows; c->cols = cols;
+    r360_calib* c = nullptr;
+    if (calib_new(ctx, rows, cols, 0, 0, &c)) return -1;
     // cameraMatrix: f = 525*cols/640, c = (cols/2-0.5, rows/2-0.5) (CloudRGBD_Ext.h:97-102;
     // equals the QVGA constant of Calib360.h:73-77 and its commented VGA line :83-85)
     const float f = 525 * (float)(cols / 640.0);
     const float cx = cols / 2 - 0.5, cy = rows / 2 - 0.5;
     const float K[9] = {f, 0, 0, 0, f, 0, cx, cy, 1};
     memcpy(c->K, K, sizeof(K));
-    for (int k = 0; k < 8; ++k)
-        for (int i = 0; i < 16; ++i) c->rt[k][i] = c->rt_inv[k][i] = (i % 5 == 0) ? 1.f : 0.f;
-    R360_HIP(hipMalloc(&c->d_rt_inv, sizeof(float) * 128));
-    R360_HIP(hipMemcpy(c->d_rt_inv, c->rt_inv, sizeof(float) * 128, hipMemcpyHostToDevice));
-    R360_HIP(hipMalloc(&c->d_rt, sizeof(float) * 128));
-    R360_HIP(hipMemcpy(c->d_rt, c->rt, sizeof(float) * 128, hipMemcpyHostToDevice));
-    if (calib_build_tables(c)) { delete c; return -1; }
     *out = c;
     return 0;
 }
@@ -468,27 +409,10 @@ extern "C" int r360_calib_create(r360_ctx* ctx, int rows, int cols, r360_calib**
 extern "C" int r360_calib_create_sphere(r360_ctx* ctx, int sph_rows, int sph_cols, r360_calib** out) {
     CHECK_ARG(ctx && out, "null arg");
     CHECK_ARG(sph_rows >= 2 && sph_cols >= 8 && sph_cols % 8 == 0, "sphere size: rows >= 2, cols a multiple of 8");
-    R360_HIP(hipSetDevice(ctx->device));
-    r360_calib* c = new r360_calib;
-    c->ctx = ctx; c->rows = 0; c->cols = 0;
-    for (int k = 0; k < 8; ++k)
-        for (int i = 0; i < 16; ++i) c->rt[k][i] = c->rt_inv[k][i] = (i % 5 == 0) ? 1.f : 0.f;
-    if (calib_build_tables(c, sph_rows, sph_cols)) { delete c; return -1; }
-    *out = c;
-    return 0;
+    return calib_new(ctx, 0, 0, sph_rows, sph_cols, out);
 }
 
-extern "C" void r360_calib_destroy(r360_calib* c) {
-    if (!c) return;
-    hipFree(c->d_rt_inv);
-    hipFree(c->d_rt);
-    hipFree(c->d_st_sinphi); hipFree(c->d_st_cosphi); hipFree(c->d_st_sinth); hipFree(c->d_st_costh);
-    for (int l = 0; l < R360_MAX_PYR; ++l) {
-        hipFree(c->trig[l].sinphi); hipFree(c->trig[l].cosphi); hipFree(c->trig[l].sinth); hipFree(c->trig[l].costh);
-    }
-    hipFree(c->clams.d_mult); hipFree(c->clams.d_counts);
-    delete c;
-}
+extern "C" void r360_calib_destroy(r360_calib* c) { delete c; }   // its owners free the tables
 
 extern "C" int r360_calib_set_extrinsics(r360_calib* c, const float* rt8) {
     CHECK_ARG(c && rt8, "null arg");
@@ -589,7 +513,7 @@ extern "C" int r360_calib_load_intrinsics(r360_calib* c, const char* dir_in) {
     std::vector<float> mult, counts;
     for (int k = 0; k < 8; ++k)
         if (read_clams(dir, k, c->clams, mult, counts)) return -1;
-    if (upload_floats(&c->clams.d_mult, mult) || upload_floats(&c->clams.d_counts, counts)) return -1;
+    if (c->upload_clams(mult, counts)) return -1;
     c->has_intrinsics = true;
     return 0;
 }
@@ -597,43 +521,7 @@ extern "C" int r360_calib_load_intrinsics(r360_calib* c, const char* dir_in) {
 // ------------------------------------------------------------------ Frame360
 extern "C" int r360_frame_create(r360_ctx* ctx, const r360_calib* calib, r360_frame** out) {
     CHECK_ARG(ctx && calib && out, "null arg");
-    R360_HIP(hipSetDevice(ctx->device));
-    r360_frame* f = new r360_frame;
-    f->ctx = ctx; f->calib = calib;
-    f->rows = calib->rows; f->cols = calib->cols;
-    f->sph_rows = calib->sph_rows; f->sph_cols = calib->sph_cols;
-    f->n_levels = calib->n_levels;
-    const size_t ns = (size_t)8 * f->rows * f->cols, nsph = (size_t)f->sph_rows * f->sph_cols;
-    if (ns) {                        // a sphere-only frame (r360_calib_create_sphere) has no sensor images
-        R360_HIP(hipMalloc(&f->d_bgr, ns * 3));
-        R360_HIP(hipMalloc(&f->d_depth, ns * 2));
-        R360_HIP(hipMalloc(&f->d_depth_m, ns * 4));
-    }
-    R360_HIP(hipMalloc(&f->d_sph_bgr, nsph * 3));
-    R360_HIP(hipMalloc(&f->d_sph_depth, nsph * 2));
-    int R = f->sph_rows, C = f->sph_cols;
-    for (int l = 0; l < f->n_levels; ++l) {
-        f->lv[l].rows = R; f->lv[l].cols = C;
-        R360_HIP(hipMalloc(&f->lv[l].p0, sizeof(float2) * (size_t)R * C));
-        R360_HIP(hipMalloc(&f->lv[l].tg, sizeof(float4) * (size_t)R * C));
-        R360_HIP(hipMalloc(&f->lv[l].pts, sizeof(float4) * (size_t)R * C));
-        if (l == 0) R360_HIP(hipMalloc(&f->lv[l].pk, sizeof(uint32_t) * (size_t)R * C));
-        R /= 2; C /= 2;
-    }
-    f->src_blocks = (int)((nsph + R360_SRC_BLOCK - 1) / R360_SRC_BLOCK);
-    R360_HIP(hipMalloc(&f->d_npts, sizeof(int) * R360_MAX_PYR));
-    R360_HIP(hipMemsetAsync(f->d_npts, 0, sizeof(int) * R360_MAX_PYR, f->ctx->stream));
-    R360_HIP(hipMalloc(&f->d_src_cnt, sizeof(int) * R360_MAX_PYR * (size_t)f->src_blocks));
-    SrcLevel sl[R360_MAX_PYR];
-    for (int l = 0; l < f->n_levels; ++l) {
-        const LevelTrig& T = calib->trig[l];
-        sl[l] = SrcLevel{f->lv[l].p0, f->lv[l].pts, T.sinphi, T.cosphi, T.sinth, T.costh, f->lv[l].rows, f->lv[l].cols};
-    }
-    R360_HIP(hipMalloc(&f->d_src_levels, sizeof(SrcLevel) * R360_MAX_PYR));
-    R360_HIP(hipMemcpy(f->d_src_levels, sl, sizeof(SrcLevel) * f->n_levels, hipMemcpyHostToDevice));
-    R360_HIP(hipEventCreateWithFlags(&f->bgr_ev, hipEventDisableTiming));
-    *out = f;
-    return 0;
+    return frame_new(ctx, calib, out);
 }
 
 // The event recorded on a frame's stream right after its last pyramid build (r360_frame_build_async).  The dense
@@ -677,13 +565,7 @@ extern "C" void r360_frame_destroy(r360_frame* f) {
     }
     // hipFree synchronises the device; the frame never dereferences its ctx here so frames may
     // outlive their context at interpreter shutdown.
-    hipFree(f->d_bgr); hipFree(f->d_depth); hipFree(f->d_depth_m); hipFree(f->d_sph_bgr); hipFree(f->d_sph_depth);
-    for (int l = 0; l < R360_MAX_PYR; ++l) { hipFree(f->lv[l].p0); hipFree(f->lv[l].tg); hipFree(f->lv[l].pts); hipFree(f->lv[l].pk); }
-    hipFree(f->d_npts); hipFree(f->d_src_cnt); hipFree(f->d_src_levels);
-    for (int l = 0; l < f->n_slevels; ++l) { hipFree(f->sp[l].p0); hipFree(f->sp[l].tg); }
-    plane_bufs_free(f);
-    if (f->bgr_ev) hipEventDestroy(f->bgr_ev);
-    delete f->sphere_cloud;
+    plane_bufs_free(f);   // joins the assembly before any memory goes
     delete f;
 }
 

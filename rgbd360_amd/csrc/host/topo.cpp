@@ -20,55 +20,26 @@
 
 int topo_allow_lds();
 
-void topo_state_free(TopoState& S) {
-    hipFree(S.A); hipFree(S.a_off); hipFree(S.gn); hipFree(S.pending[0]); hipFree(S.pending[1]);
-    hipFree(S.idx[0]); hipFree(S.idx[1]); hipFree(S.label); hipFree(S.rec); hipFree(S.scratch); hipFree(S.count);
-    hipFree(S.hook_d); hipFree(S.hook_i);
-    hipHostFree(S.h_count);
-    S = TopoState();
-}
-
 namespace {
 
 constexpr int MAXN = R360_TOPO_MAX_NODES;
 
-template <class T>
-int regrow(r360_ctx* ctx, T*& p, size_t need) {
-    if (p) {
-        if (ctx_wait(ctx)) return -1;
-        R360_HIP(hipFree(p));
-        p = nullptr;
-    }
-    R360_HIP(hipMalloc(&p, sizeof(T) * std::max<size_t>(need, 1)));
-    return 0;
-}
-
+// every buffer of the context's TopoState (DevBuf / PinnedBuf members, freed with the context) is sized to exactly
+// what the call needs, and decides from its own capacity
 int reserve(r360_ctx* ctx, int graphs, size_t floats) {
     TopoState& S = ctx->topo;
     if (!S.lds_attr) {
         if (topo_allow_lds()) return -1;
         S.lds_attr = true;
     }
-    if (!S.count) {
-        R360_HIP(hipMalloc(&S.count, sizeof(int)));
-        R360_HIP(hipHostMalloc(&S.h_count, sizeof(int), hipHostMallocDefault));
-        R360_HIP(hipMalloc(&S.hook_d, sizeof(double) * 2 * MAXN));
-        R360_HIP(hipMalloc(&S.hook_i, sizeof(int) * MAXN));
-    }
-    if (graphs > S.cap_graphs) {
-        const size_t g = graphs;
-        if (regrow(ctx, S.a_off, g) || regrow(ctx, S.gn, g) || regrow(ctx, S.pending[0], g * MAXN) ||
-            regrow(ctx, S.pending[1], g * MAXN) || regrow(ctx, S.idx[0], g * MAXN) || regrow(ctx, S.idx[1], g * MAXN) ||
-            regrow(ctx, S.label, g * MAXN) || regrow(ctx, S.rec, g * 2 * MAXN) ||
-            regrow(ctx, S.scratch, g * 2 * MAXN * MAXN))
-            return -1;
-        S.cap_graphs = graphs;
-    }
-    if (floats > S.cap_A) {
-        if (regrow(ctx, S.A, floats)) return -1;
-        S.cap_A = floats;
-    }
-    return 0;
+    if (S.count.reserve(ctx, 1) || S.h_count.reserve(ctx, 1) || S.hook_d.reserve(ctx, 2 * MAXN) || S.hook_i.reserve(ctx, MAXN))
+        return -1;
+    const size_t g = graphs;
+    if (S.a_off.reserve(ctx, g) || S.gn.reserve(ctx, g) || S.pending[0].reserve(ctx, g * MAXN) ||
+        S.pending[1].reserve(ctx, g * MAXN) || S.idx[0].reserve(ctx, g * MAXN) || S.idx[1].reserve(ctx, g * MAXN) ||
+        S.label.reserve(ctx, g * MAXN) || S.rec.reserve(ctx, g * 2 * MAXN) || S.scratch.reserve(ctx, g * 2 * MAXN * MAXN))
+        return -1;
+    return S.A.reserve(ctx, floats);
 }
 
 int check_params(const r360_topo_params* p) {
@@ -121,16 +92,16 @@ int run_chunk(r360_ctx* ctx, int count, const float* const* A, const int* n, con
         for (int i = 0; i < n[g]; ++i) idx0[(size_t)g * MAXN + i] = i;
         pend[g] = TopoCluster{g, 0, n[g], 0};
     }
-    R360_HIP(hipMemcpyAsync(S.A, packed.data(), sizeof(float) * floats, hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(S.a_off, a_off.data(), sizeof(long long) * count, hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(S.gn, n, sizeof(int) * count, hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(S.idx[0], idx0.data(), sizeof(int) * idx0.size(), hipMemcpyHostToDevice, st));
-    R360_HIP(hipMemcpyAsync(S.pending[0], pend.data(), sizeof(TopoCluster) * count, hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(S.A.get(), packed.data(), sizeof(float) * floats, hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(S.a_off.get(), a_off.data(), sizeof(long long) * count, hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(S.gn.get(), n, sizeof(int) * count, hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(S.idx[0].get(), idx0.data(), sizeof(int) * idx0.size(), hipMemcpyHostToDevice, st));
+    R360_HIP(hipMemcpyAsync(S.pending[0].get(), pend.data(), sizeof(TopoCluster) * count, hipMemcpyHostToDevice, st));
     TopoArgs a;
-    a.A = S.A; a.a_off = S.a_off; a.gn = S.gn;
-    a.next_count = S.count;
-    a.label = S.label;
-    a.scratch = S.scratch;
+    a.A = S.A.get(); a.a_off = S.a_off.get(); a.gn = S.gn.get();
+    a.next_count = S.count.get();
+    a.label = S.label.get();
+    a.scratch = S.scratch.get();
     a.threshold = p.threshold_ncut;
     a.min_cluster = p.min_cluster;
     a.recursive = p.recursive ? 1 : 0;
@@ -140,30 +111,30 @@ int run_chunk(r360_ctx* ctx, int count, const float* const* A, const int* n, con
             r360_set_error("topo: the recursion queued more clusters than a graph has nodes");
             return -1;
         }
-        a.pending = S.pending[level & 1];
-        a.next = S.pending[1 - (level & 1)];
-        a.idx_in = S.idx[level & 1];
-        a.idx_out = S.idx[1 - (level & 1)];
-        a.rec = S.rec + done;
+        a.pending = S.pending[level & 1].get();
+        a.next = S.pending[1 - (level & 1)].get();
+        a.idx_in = S.idx[level & 1].get();
+        a.idx_out = S.idx[1 - (level & 1)].get();
+        a.rec = S.rec.get() + done;
         const bool hooked = hook && level == 0;
-        a.eig_out = hooked ? S.hook_d : nullptr;
-        a.fiedler_out = hooked ? S.hook_d + MAXN : nullptr;
-        a.side_out = hooked ? S.hook_i : nullptr;
-        R360_HIP(hipMemsetAsync(S.count, 0, sizeof(int), st));
+        a.eig_out = hooked ? S.hook_d.get() : nullptr;
+        a.fiedler_out = hooked ? S.hook_d.get() + MAXN : nullptr;
+        a.side_out = hooked ? S.hook_i.get() : nullptr;
+        R360_HIP(hipMemsetAsync(S.count.get(), 0, sizeof(int), st));
         if (launch_topo_level(st, a, pending)) return -1;
-        R360_HIP(hipMemcpyAsync(S.h_count, S.count, sizeof(int), hipMemcpyDeviceToHost, st));
+        R360_HIP(hipMemcpyAsync(S.h_count.get(), S.count.get(), sizeof(int), hipMemcpyDeviceToHost, st));
         if (ctx_wait(ctx)) return -1;   // the level's read-back: the clusters it queued
         done += pending;
-        pending = *S.h_count;
+        pending = *S.h_count.get();
     }
     std::vector<int> label((size_t)count * MAXN);
     std::vector<TopoRecord> r(done);
-    R360_HIP(hipMemcpy(label.data(), S.label, sizeof(int) * label.size(), hipMemcpyDeviceToHost));
-    R360_HIP(hipMemcpy(r.data(), S.rec, sizeof(TopoRecord) * done, hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(label.data(), S.label.get(), sizeof(int) * label.size(), hipMemcpyDeviceToHost));
+    R360_HIP(hipMemcpy(r.data(), S.rec.get(), sizeof(TopoRecord) * done, hipMemcpyDeviceToHost));
     if (hook) {
-        if (hook->side) R360_HIP(hipMemcpy(hook->side, S.hook_i, sizeof(int) * n[0], hipMemcpyDeviceToHost));
-        if (hook->eig) R360_HIP(hipMemcpy(hook->eig, S.hook_d, sizeof(double) * n[0], hipMemcpyDeviceToHost));
-        if (hook->fiedler) R360_HIP(hipMemcpy(hook->fiedler, S.hook_d + MAXN, sizeof(double) * n[0], hipMemcpyDeviceToHost));
+        if (hook->side) R360_HIP(hipMemcpy(hook->side, S.hook_i.get(), sizeof(int) * n[0], hipMemcpyDeviceToHost));
+        if (hook->eig) R360_HIP(hipMemcpy(hook->eig, S.hook_d.get(), sizeof(double) * n[0], hipMemcpyDeviceToHost));
+        if (hook->fiedler) R360_HIP(hipMemcpy(hook->fiedler, S.hook_d.get() + MAXN, sizeof(double) * n[0], hipMemcpyDeviceToHost));
     }
     std::sort(r.begin(), r.end(), [](const TopoRecord& x, const TopoRecord& y) {
         if (x.graph != y.graph) return x.graph < y.graph;

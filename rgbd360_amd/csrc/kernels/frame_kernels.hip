@@ -799,18 +799,7 @@ int launch_src_compaction(r360_frame* f, unsigned levels) {
 // launch.  Levels are allocated on first use.
 int launch_sensor_pyramid(r360_frame* f) {
     const float min_d = 0.3f, max_d = 6.0f;
-    if (!f->n_slevels) {
-        int R = f->rows, C = f->cols, nl = 0;
-        while (nl < R360_MAX_PYR) {
-            f->sp[nl].rows = R; f->sp[nl].cols = C;
-            R360_HIP(hipMalloc(&f->sp[nl].p0, sizeof(float2) * 8 * (size_t)R * C));
-            R360_HIP(hipMalloc(&f->sp[nl].tg, sizeof(float4) * 8 * (size_t)R * C));
-            ++nl;
-            if ((R & 1) || (C & 1) || R < 8 || C < 8) break;   // cv::pyrDown halves exactly only even sizes
-            R /= 2; C /= 2;
-        }
-        f->n_slevels = nl;
-    }
+    if (f->alloc_sensor_pyramid()) return -1;
     hipStream_t st = f->ctx->stream;
     const long n0 = 8L * f->rows * f->cols;
     if (n0 > 0x7fffffffL) {   // k_pyramid's 32-bit pixel indices

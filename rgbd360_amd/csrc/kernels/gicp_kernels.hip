@@ -342,8 +342,8 @@ int launch_gicp_knn_cov(hipStream_t st, const GicpCloud& C, float eps) {
     if (C.k < 1 || C.k > R360_GICP_KMAX || (size_t)C.k > C.n) { r360_set_error("gicp: k outside the kernel's range"); return -1; }
     const size_t lds = (size_t)C.k * KNN_TPB * (sizeof(double) + sizeof(int));
     const unsigned nb = (unsigned)((C.n + KNN_TPB - 1) / KNN_TPB);
-    hipLaunchKernelGGL(k_gicp_knn_cov, dim3(nb), dim3(KNN_TPB), lds, st, C.pts, C.spts, C.cell_start, C.grid,
-                       (unsigned)C.n, C.k, (double)eps, C.knn, C.cov6);
+    hipLaunchKernelGGL(k_gicp_knn_cov, dim3(nb), dim3(KNN_TPB), lds, st, C.pts.get(), C.spts.get(), C.cell_start.get(), C.grid,
+                       (unsigned)C.n, C.k, (double)eps, C.knn.get(), C.cov6.get());
     R360_HIP(hipGetLastError());
     return 0;
 }
@@ -352,8 +352,8 @@ int launch_gicp_corr(hipStream_t st, const GicpCloud& S, const GicpCloud& T, con
                      int* corr, double* M6, double* d2) {
     if (S.n == 0) return 0;
     const unsigned nb = (unsigned)((S.n + TPB - 1) / TPB);
-    hipLaunchKernelGGL(k_gicp_corr, dim3(nb), dim3(TPB), 0, st, S.pts, S.cov6, (unsigned)S.n, T.spts, T.cell_start, T.cov6,
-                       T.grid, X, gate2, want_m, corr, M6, d2);
+    hipLaunchKernelGGL(k_gicp_corr, dim3(nb), dim3(TPB), 0, st, S.pts.get(), S.cov6.get(), (unsigned)S.n, T.spts.get(),
+                       T.cell_start.get(), T.cov6.get(), T.grid, X, gate2, want_m, corr, M6, d2);
     R360_HIP(hipGetLastError());
     return 0;
 }
@@ -361,7 +361,7 @@ int launch_gicp_corr(hipStream_t st, const GicpCloud& S, const GicpCloud& T, con
 int launch_gicp_pass(hipStream_t st, const GicpCloud& S, const GicpCloud& T, const GicpPose& Y, const int* corr,
                      const double* M6, double* partials, double* sums) {
     const int nb = gicp_pass_blocks(S.n);
-    hipLaunchKernelGGL(k_gicp_pass, dim3(nb), dim3(TPB), 0, st, S.pts, (unsigned)S.n, T.pts, Y, corr, M6, partials);
+    hipLaunchKernelGGL(k_gicp_pass, dim3(nb), dim3(TPB), 0, st, S.pts.get(), (unsigned)S.n, T.pts.get(), Y, corr, M6, partials);
     R360_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_gicp_final, dim3(1), dim3(64 * FINAL_WAVES), 0, st, partials, nb, W, sums);
     R360_HIP(hipGetLastError());

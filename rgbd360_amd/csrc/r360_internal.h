@@ -223,61 +223,6 @@ struct RegionPart {
     float bmin[3], bmax[3];
 };
 
-// Device buffers of a frame's plane half (allocated on the first CLOUD/PLANES build)
-struct PlaneBufs {
-    int w = 0, h = 0;
-    float4* cloud = nullptr;    // [8][h][w] {x, y, z, 0}
-    uchar4* rgb = nullptr;      // [8][h][w] {r, g, b, 0}
-    float4* nrm = nullptr;      // [8][h][w] {nx, ny, nz, d = p.n}
-    float* dist0 = nullptr;     // distance-map init (depth-change map)
-    float* dist = nullptr;      // distance map
-    float2* grids = nullptr;    // bilateral grids, 8 x 2 x grid_cells
-    long grid_cells = 0;
-    int sd_max = 0;
-    int* zmm = nullptr;         // per-sensor depth range for the bilateral grid: [8] min, [8] max (ordered ints)
-    int* parent = nullptr;      // union-find parents, then root ranks
-    int* root = nullptr;
-    int* lab = nullptr;         // CCL labels (per-sensor ids, -1 none)
-    int* labf = nullptr;        // labels after refinement
-    int* cnt = nullptr;         // label sizes [8][N]
-    int* aux = nullptr;         // the large labels' first pixels [8][R360_MAX_BIG] (plane_seg.hip)
-    int* chunk = nullptr;       // per-chunk counts of the numbering kernels [8][ceil(N / 256)]
-    int* nlab = nullptr;        // [8]
-    int* big = nullptr;         // [8][R360_MAX_BIG]
-    int* nbig = nullptr;        // [8]
-    r360p::Moments* mom = nullptr;   // [8][R360_MAX_BIG] the large labels' moments
-    PlaneModel* models = nullptr;    // [8][R360_MAX_MODELS]
-    int* nmodels = nullptr;          // [8]
-    int8_t* state = nullptr;         // refinement state [8][N]
-    int8_t* state2 = nullptr;        // refinement state after the first sweep [8][N]
-    int8_t* rbnd = nullptr;          // banded refinement: each band's assignments into the next band's first row
-    int* rflag = nullptr;            //   [8][R360_REFINE_BANDS][w] and whether they changed that row [8][..]
-    unsigned long long* mask = nullptr;  // closeness masks [8][N]
-    uint16_t* rcode = nullptr;           // wavefront refinement, skewed [8][h + w - 1][h]: state | push conditions
-    unsigned long long* rmsk = nullptr;  //   closeness masks, skewed
-    int8_t* rf1 = nullptr;               //   first sweep's states, skewed
-    int8_t* rf2 = nullptr;               //   second sweep's states, skewed
-    PlaneOut* out = nullptr;         // [8][R360_MAX_MODELS]
-    RegionPart* gpart = nullptr;     // [R360_GM_COPIES][8][R360_MAX_MODELS] region accumulators (k_gm<true>)
-    float4* contour = nullptr;       // contour points kept by the hull prefilter (pinned host)
-    long contour_cap = 0;
-    VoxOut* vox = nullptr;           // voxel-fallback centroids kept by the hull prefilter (pinned host)
-    float4* contour_dev = nullptr;   // the traced contours (device; k_trace -> k_hullpre)
-    VoxOut* vox_dev = nullptr;       // all voxel-fallback centroids (device; k_vox_compact -> k_hullpre)
-    long vox_cap = 0;
-    long* totals = nullptr;          // [2] pool usage
-    int* err = nullptr;              // error bits
-    // pinned host mirrors
-    PlaneOut* h_out = nullptr;
-    int* h_nmodels = nullptr;        // [8], then err at [8], totals at (long*)(h_nmodels + 10)
-    // host assembly thread (planes_enqueue -> planes_finish)
-    hipEvent_t done = nullptr;
-    hipEvent_t ready = nullptr;      // plane queue: recorded on the frame's stream once its inputs are built
-    std::shared_ptr<struct PlaneTicket> ticket;   // plane queue: set when the batch's kernels and `done` are enqueued
-    bool asm_busy = false;           // the host assembly is queued or running (host/pbmap.cpp AsmPool; under its lock)
-    int worker_rc = 0;
-    std::string worker_err;
-};
 struct PbMapHost;                    // host PbMap (host/pbmap.cpp)
 struct LocalPlanesHost;              // the sensors' planes before grouping (R360_BUILD_LOCAL_PLANES; host/pbmap.cpp)
 
@@ -302,6 +247,54 @@ struct PlaneDev {
 struct PlaneBatch { PlaneDev f[R360_PLANE_BATCH]; };
 static_assert(sizeof(PlaneBatch) + 256 <= 4096, "the plane batch travels as a kernel argument");
 
+// A handle's sized-once device and pinned buffers: each is taken once, its raw pointer goes to the view that names it
+// (LevelBufs, LevelTrig, PlaneDev, a d_* field), and all are freed together.  An allocation is hipMalloc /
+// hipHostMalloc of exactly items * sizeof(T) bytes; on failure the thread's error is set and the view is left null.
+struct BufSet {
+    std::vector<DevBuf<unsigned char>> dev;
+    std::vector<PinnedBuf<unsigned char>> pin;
+    template <class T>
+    int take(T*& view, size_t items) {
+        dev.emplace_back();
+        const int rc = dev.back().reserve(nullptr, sizeof(T) * items);
+        view = reinterpret_cast<T*>(dev.back().get());
+        return rc;
+    }
+    template <class T>
+    int take_pinned(T*& view, size_t items) {
+        pin.emplace_back();
+        const int rc = pin.back().reserve(nullptr, sizeof(T) * items);
+        view = reinterpret_cast<T*>(pin.back().get());
+        return rc;
+    }
+    void release() { dev.clear(); pin.clear(); }
+};
+
+// A frame's plane half (allocated on the first CLOUD/PLANES build): the owner of its device and pinned buffers and
+// of its two events, and the view of them the kernels take.  alloc() (host/handles.cpp) is the one place that names
+// each buffer with its size and says what it holds.
+struct PlaneBufs {
+    int w = 0, h = 0;
+    long grid_cells = 0;
+    int sd_max = 0;
+    BufSet mem;                      // owns every buffer v names, except the ones plane_dev() patches in
+    PlaneDev v{};                    // v.cloud != nullptr: the whole set is there
+    // host assembly thread (planes_enqueue -> planes_finish)
+    hipEvent_t done = nullptr;
+    hipEvent_t ready = nullptr;      // plane queue: recorded on the frame's stream once its inputs are built
+    std::shared_ptr<struct PlaneTicket> ticket;   // plane queue: set when the batch's kernels and `done` are enqueued
+    bool asm_busy = false;           // the host assembly is queued or running (host/pbmap.cpp AsmPool; under its lock)
+    int worker_rc = 0;
+    std::string worker_err;
+    PlaneBufs() = default;
+    PlaneBufs(const PlaneBufs&) = delete;
+    PlaneBufs& operator=(const PlaneBufs&) = delete;
+    ~PlaneBufs() { release(); }
+    // the buffers and events of a frame with sensors of rows x cols pixels: 0, or -1 with the error set and nothing held
+    int alloc(int rows, int cols);
+    void release();                  // everything back to the empty state; the caller has joined the assembly
+};
+
 // ------------------------------------------------------------------ voxel grid / global map
 // (kernels/map_kernels.hip, host/map.cpp)
 // A point travels as 16 bytes: the bits of x, y, z and the PointXYZRGBA-packed colour.
@@ -322,32 +315,23 @@ struct MapGrid { float inv; int minb[3]; unsigned dx, dy; };   // dx, dy: the gr
 struct MapRig { float rt[8][16]; };                            // Rt_[sensor], column-major (a kernel argument)
 struct MapPose { float m[16]; };
 constexpr size_t R360_MAP_SCAN_BLOCK = 2048;                   // bitmap words per workgroup of the popcount scan
-// Everything the voxel filter and the context's map hold on the device: plain pointers owned by the r360_ctx and
-// freed by map_state_free from r360_ctx_destroy.
+// Everything the voxel filter and the context's map hold on the device: DevBuf / PinnedBuf members of the r360_ctx,
+// grown on demand (host/map.cpp does the arithmetic) and freed with the context.
 struct MapState {
-    MapHdr* d_hdr = nullptr;
-    MapHdr* h_hdr = nullptr;             // pinned
-    MapCell* table = nullptr;            // all cells zero between calls
-    size_t table_cap = 0;
-    unsigned* list = nullptr;            // [table_cap / 2] cells claimed by the running call
-    size_t list_cap = 0;
-    unsigned* bitmap = nullptr;          // occupancy of the bounding grid, one bit per voxel
-    unsigned* wprefix = nullptr;         // exclusive prefix of the bitmap words' popcounts
-    size_t bitmap_cap = 0, wprefix_cap = 0;
-    unsigned* bsum = nullptr;            // per-workgroup popcounts of the scan
-    size_t bsum_cap = 0;
-    float* up_xyz = nullptr;             // staging of host arrays: up_xyz_cap floats, up_rgba_cap colours
-    uint32_t* up_rgba = nullptr;
-    size_t up_xyz_cap = 0, up_rgba_cap = 0;
-    uint4* in = nullptr;                 // r360_cloud_filter_voxel's packed input and output
-    uint4* out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
-    uint4* map[2] = {nullptr, nullptr};  // the context's map: map[cur][0 .. map_n), the other buffer takes the next result
-    size_t map_cap[2] = {0, 0};
+    DevBuf<MapHdr> d_hdr;
+    PinnedBuf<MapHdr> h_hdr;
+    DevBuf<MapCell> table;               // a power of two of cells (cap() is the probe mask + 1), all zero between calls
+    DevBuf<unsigned> list;               // [table.cap() / 2] cells claimed by the running call
+    DevBuf<unsigned> bitmap;             // occupancy of the bounding grid, one bit per voxel
+    DevBuf<unsigned> wprefix;            // exclusive prefix of the bitmap words' popcounts
+    DevBuf<unsigned> bsum;               // per-workgroup popcounts of the scan
+    DevBuf<float> up_xyz;                // staging of host arrays
+    DevBuf<uint32_t> up_rgba;
+    DevBuf<uint4> in, out;               // r360_cloud_filter_voxel's packed input and output
+    DevBuf<uint4> map[2];                // the context's map: map[cur][0 .. map_n), the other buffer takes the next result
     size_t map_n = 0;
     int cur = 0;
 };
-void map_state_free(MapState& M);
 int launch_map_pack_host(hipStream_t st, const float* xyz, const uint32_t* rgba, size_t n, uint4* out);
 int launch_map_pack_frame(hipStream_t st, const float4* cloud, const uchar4* rgb, size_t per_sensor, const MapRig& rig,
                           const MapPose& pose, float x_min, float x_max, float box, uint4* out);
@@ -412,29 +396,26 @@ int launch_out_compact(hipStream_t st, const uint4* pts, size_t n, const unsigne
 constexpr int R360_GICP_KMAX = 32;      // k_correspondences the kNN kernel's LDS lists hold
 constexpr int R360_GICP_W = 29;         // one inner pass's sums: f, g (6), H upper triangle (21), n_corr
 constexpr int R360_GICP_MAXB = 256;     // workgroups (= partial records) of the inner pass at most
-struct GicpCloud {
-    size_t n = 0, cap = 0, spts_cap = 0, cov_cap = 0, cells = 0, cells_cap = 0;
+struct GicpCloud {                      // the handle's owner of one cloud; launchers take it by const& and read get()
+    size_t n = 0, cells = 0;
     int k = 0;
     GicpGrid grid{};
-    float4* pts = nullptr;              // kept points in input order {x, y, z, 0}
-    float4* spts = nullptr;             // the same points ordered by cell, w = the point's index (bits)
-    unsigned* cell_start = nullptr;     // [cells + 1] first sorted point of every cell
-    double* cov6 = nullptr;             // [n][6] upper triangle xx xy xz yy yz zz of C_i (fp64: M_i inverts sums of them)
-    int* knn = nullptr;                 // [n][k] neighbour indices, ascending (distance, index)
-    size_t knn_cap = 0;
+    DevBuf<float4> pts;                 // kept points in input order {x, y, z, 0}
+    DevBuf<float4> spts;                // the same points ordered by cell, w = the point's index (bits)
+    DevBuf<unsigned> cell_start;        // [cells + 1] first sorted point of every cell
+    DevBuf<double> cov6;                // [n][6] upper triangle xx xy xz yy yz zz of C_i (fp64: M_i inverts sums of them)
+    DevBuf<int> knn;                    // [n][k] neighbour indices, ascending (distance, index)
 };
 struct GicpPose { double m[12]; };      // row-major 3 x 4 [R | t]
 struct GicpState {
     GicpCloud src, tgt;
-    int* corr = nullptr;                // [src.n] j(i), -1 = none
-    double* M6 = nullptr;               // [src.n][6] upper triangle of M_i
-    double* d2 = nullptr;               // [src.n] squared distance to j(i)
-    size_t corr_cap = 0;
-    double* partials = nullptr;         // [R360_GICP_MAXB][R360_GICP_W]
-    double* d_sums = nullptr;           // [R360_GICP_W]
-    double* h_sums = nullptr;           // pinned
+    DevBuf<int> corr;                   // [src.n] j(i), -1 = none
+    DevBuf<double> M6;                  // [src.n][6] upper triangle of M_i
+    DevBuf<double> d2;                  // [src.n] squared distance to j(i)
+    DevBuf<double> partials;            // [R360_GICP_MAXB][R360_GICP_W]
+    DevBuf<double> d_sums;              // [R360_GICP_W]
+    PinnedBuf<double> h_sums;
 };
-void gicp_state_free(GicpState& S);
 int launch_gicp_knn_cov(hipStream_t st, const GicpCloud& C, float eps);
 int launch_gicp_corr(hipStream_t st, const GicpCloud& S, const GicpCloud& T, const GicpPose& X, double gate2, int want_m,
                      int* corr, double* M6, double* d2);
@@ -550,24 +531,21 @@ struct TopoArgs {
     double* fiedler_out = nullptr;  // vector and the sides (1 / 2), R360_TOPO_MAX_NODES each; NULL otherwise
     int* side_out = nullptr;
 };
-struct TopoState {
-    int cap_graphs = 0;
-    size_t cap_A = 0;
-    float* A = nullptr;
-    long long* a_off = nullptr;
-    int* gn = nullptr;
-    TopoCluster* pending[2] = {nullptr, nullptr};
-    int* idx[2] = {nullptr, nullptr};
-    int* label = nullptr;
-    TopoRecord* rec = nullptr;
-    double* scratch = nullptr;
-    int* count = nullptr;
-    int* h_count = nullptr;         // pinned
-    double* hook_d = nullptr;       // [2][R360_TOPO_MAX_NODES]
-    int* hook_i = nullptr;          // [R360_TOPO_MAX_NODES]
+struct TopoState {                  // every buffer holds exactly what the largest call so far needed
+    DevBuf<float> A;
+    DevBuf<long long> a_off;
+    DevBuf<int> gn;
+    DevBuf<TopoCluster> pending[2];
+    DevBuf<int> idx[2];
+    DevBuf<int> label;
+    DevBuf<TopoRecord> rec;
+    DevBuf<double> scratch;
+    DevBuf<int> count;
+    PinnedBuf<int> h_count;
+    DevBuf<double> hook_d;          // [2][R360_TOPO_MAX_NODES]
+    DevBuf<int> hook_i;             // [R360_TOPO_MAX_NODES]
     bool lds_attr = false;
 };
-void topo_state_free(TopoState& S);
 int launch_topo_level(hipStream_t st, const TopoArgs& a, int n_pending);
 
 // ------------------------------------------------------------------ host objects
@@ -705,6 +683,8 @@ struct ClamsDev {
     float* d_counts = nullptr;  // [8][ny*nx][num_bins]
 };
 
+// The raw pointers below (d_*, trig[], clams.d_*) are the views the launchers and SrcLevel copy; `mem` owns what
+// alloc() takes at creation, clams_mult / clams_counts own the CLAMS tables, and the destructor frees them all.
 struct r360_calib {
     r360_ctx* ctx = nullptr;
     int rows = 0, cols = 0;
@@ -724,7 +704,18 @@ struct r360_calib {
     // ICP trig tables per pyramid level of the sphere
     int n_levels = 0;
     LevelTrig trig[R360_MAX_PYR];
+    BufSet mem;
+    DevBuf<float> clams_mult, clams_counts;
+    // Identity extrinsics (rows > 0: uploaded to d_rt_inv, d_rt), then the stitch tables (rows > 0) and the trig tables of
+    // the sphere's levels.  sph_rows / sph_cols: the sphere size; 0 = the one stitchSphericalImage produces from the
+    // sensors (width 8 * rows, height width / 6, Frame360.h:391-392).  0, or -1 with the error set.
+    int alloc(int sph_rows, int sph_cols);
+    // the CLAMS tables replaced: the old ones are released first (hipFree drains the device, so no enqueued kernel still
+    // reads them), then the new ones allocated and copied with a blocking hipMemcpy
+    int upload_clams(const std::vector<float>& mult, const std::vector<float>& counts);
 };
+// new + alloc; on failure the handle and all it holds are released, the error is set and *out is untouched (host/handles.cpp)
+int calib_new(r360_ctx* ctx, int rows, int cols, int sph_rows, int sph_cols, r360_calib** out);
 
 // Host copy of Frame360::sphereCloud as loadCloud leaves it (io.cpp)
 struct SphereCloudHost {
@@ -759,6 +750,9 @@ struct r360_frame {
     // R360_BUILD_* stages done (atomic: a frame built on one thread may have its sphere built from another,
     // while the first reads its plane flags)
     std::atomic<unsigned> built{0};
+    // the owners of the device memory named above: `mem` what alloc() takes at creation (the images, lv[], d_npts,
+    // d_src_cnt, d_src_levels), `sp_mem` the sensor pyramid's levels (alloc_sensor_pyramid, on first use)
+    BufSet mem, sp_mem;
     PlaneBufs pl;
     PbMapHost* pbmap = nullptr;
     LocalPlanesHost* local = nullptr;  // kept by a build with R360_BUILD_LOCAL_PLANES, else null
@@ -779,7 +773,17 @@ struct r360_frame {
     // it at submit and its batch refuses to run if the frame was rebuilt meanwhile (the event would then stand for
     // the newer build)
     std::atomic<unsigned> build_gen{0};
+    // The creation-time buffers for ctx / calib (set before the call), d_npts zeroed on the context's stream, the level
+    // table uploaded, bgr_ev created.  0, or -1 with the error set.
+    int alloc();
+    // sp[] for the sensors' size and n_slevels; on failure the levels taken so far are released and n_slevels stays 0
+    int alloc_sensor_pyramid();
+    // frees the memory and bgr_ev and deletes sphere_cloud; never dereferences ctx (frames may outlive it at interpreter
+    // shutdown).  pbmap and local are gone by then: plane_bufs_free deletes them after joining the assembly
+    ~r360_frame();
 };
+// new + alloc; on failure the handle and all it holds are released, the error is set and *out is untouched (host/handles.cpp)
+int frame_new(r360_ctx* ctx, const r360_calib* calib, r360_frame** out);
 
 // ------------------------------------------------------------------ kernel launchers
 hipStream_t capture_stream(r360_ctx* ctx);   // ctx->cap_stream, created on first use (nullptr on failure)

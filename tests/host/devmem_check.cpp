@@ -2,10 +2,13 @@
 // allocations with a live set, a "fail the k-th allocation" switch and a log of the calls in order.  Built by
 // tests/test_devmem_host.py with g++ and the address / undefined-behaviour sanitizers, no HIP runtime linked; exits
 // non-zero, naming the broken rule, when an owner leaks, dangles, frees twice, allocates without need, frees a live
-// buffer without waiting first, or zeroes at the wrong time.
+// buffer without waiting first, or zeroes at the wrong time.  It also builds the memory part of the sized-once handles
+// (rgbd360_amd/csrc/host/handles.cpp: calibration, frame, plane buffers, sensor pyramid) and makes every allocator,
+// event, copy and memset call of each creation fail in turn: the creation must fail clean and then succeed.
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <set>
 #include <string>
 #include <type_traits>
@@ -20,11 +23,18 @@ static std::vector<std::string> g_log;
 static int g_allocs = 0, g_fail_at = 0, g_errors = 0, g_wait_rc = 0;
 static size_t g_last_bytes = 0, g_memset_bytes = 0;
 static hipStream_t g_memset_stream = nullptr;
+// every call that can fail (allocator, event creation, copy, memset) counts here, and call number g_fail_call fails
+static int g_calls = 0, g_fail_call = 0;
+static std::set<hipEvent_t> g_events;
+static std::vector<size_t> g_sizes;   // the allocations' bytes, in order
+static bool fail_here() { return ++g_calls == g_fail_call; }
 
 static hipError_t mock_alloc(const char* what, void** p, size_t n) {
     g_log.push_back(what);
     g_last_bytes = n;
-    if (++g_allocs == g_fail_at) {
+    g_sizes.push_back(n);
+    const bool fail_call = fail_here();
+    if (++g_allocs == g_fail_at || fail_call) {
         *p = (void*)0x1;   // a failed call leaves no usable pointer behind
         return hipErrorOutOfMemory;
     }
@@ -51,11 +61,37 @@ hipError_t hipFree(void* p) { return mock_free("free", p); }
 hipError_t hipHostFree(void* p) { return mock_free("hostfree", p); }
 hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t st) {
     g_log.push_back("memset");
+    if (fail_here()) return hipErrorInvalidValue;
     if (!g_live.count(p) || v != 0) { fprintf(stderr, "FAIL: memset of a buffer that is not live, or not to zero\n"); exit(1); }
     g_memset_bytes = n;
     g_memset_stream = st;
     return hipSuccess;
 }
+hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind kind) {
+    g_log.push_back("memcpy");
+    if (fail_here()) return hipErrorInvalidValue;
+    if (kind != hipMemcpyHostToDevice || !g_live.count(dst)) {
+        fprintf(stderr, "FAIL: memcpy that is not an upload to the start of a live buffer\n");
+        exit(1);
+    }
+    if (n) memcpy(dst, src, n);   // the address sanitizer sees a copy past either end
+    return hipSuccess;
+}
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) {
+    g_log.push_back("event");
+    if (fail_here()) return hipErrorOutOfMemory;   // *e is left as it was
+    *e = (hipEvent_t)malloc(1);
+    g_events.insert(*e);
+    return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t e) {
+    g_log.push_back("eventdestroy");
+    if (!g_events.erase(e)) { fprintf(stderr, "FAIL: hipEventDestroy of an event that is not live\n"); exit(1); }
+    free(e);
+    return hipSuccess;
+}
+hipError_t hipSetDevice(int) { return hipSuccess; }
+hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { g_log.push_back("streamsync"); return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "mock error"; }
 
@@ -76,7 +112,10 @@ static std::string log_str() {
     for (const std::string& e : g_log) s += (s.empty() ? "" : " ") + e;
     return s;
 }
-static void fresh() { g_log.clear(); g_allocs = 0; g_fail_at = 0; g_errors = 0; g_wait_rc = 0; }
+static void fresh() {
+    g_log.clear(); g_sizes.clear();
+    g_allocs = 0; g_fail_at = 0; g_errors = 0; g_wait_rc = 0; g_calls = 0; g_fail_call = 0;
+}
 
 static_assert(sizeof(DevBuf<int>) == sizeof(int*) + sizeof(size_t), "an owner is a pointer and a capacity");
 static_assert(sizeof(PinnedBuf<int>) == sizeof(int*) + sizeof(size_t), "an owner is a pointer and a capacity");
@@ -87,6 +126,9 @@ static_assert(std::is_trivially_copyable<PgoDev>::value, "PgoDev");
 static_assert(std::is_trivially_copyable<RigcalDev>::value, "RigcalDev");
 static_assert(std::is_trivially_copyable<TopoArgs>::value, "TopoArgs");
 static_assert(std::is_trivially_copyable<PlaneDev>::value, "PlaneDev");
+static_assert(std::is_trivially_copyable<LevelBufs>::value, "LevelBufs");
+static_assert(std::is_trivially_copyable<LevelTrig>::value, "LevelTrig");
+static_assert(std::is_trivially_copyable<SrcLevel>::value, "SrcLevel");
 
 template <class Buf>
 static void basic(const char* alloc, const char* release) {
@@ -209,7 +251,123 @@ static void sequence() {
         }
 }
 
+// ------------------------------------------------------------------ the sized-once handles (host/handles.cpp)
+// Runs `make` once to count the calls that can fail, N, then N times with call k failing: it must return non-zero with
+// the error set and leave the live buffers and events as it found them; the same call then succeeds, and `drop`
+// releases it cleanly (a free of anything not live ends the program in the mock).  Returns N.
+template <class Make, class Drop>
+static int fail_each(Make make, Drop drop) {
+    const size_t live0 = g_live.size(), ev0 = g_events.size();
+    fresh();
+    CHECK(make() == 0);
+    const int N = g_calls;
+    CHECK(N > 0);
+    drop();
+    CHECK(g_live.size() == live0 && g_events.size() == ev0);
+    for (int k = 1; k <= N; ++k) {
+        fresh();
+        g_fail_call = k;
+        CHECK(make() != 0 && g_errors >= 1);
+        CHECK(g_live.size() == live0 && g_events.size() == ev0);
+        g_fail_call = 0;
+        CHECK(make() == 0);
+        drop();
+        CHECK(g_live.size() == live0 && g_events.size() == ev0);
+    }
+    return N;
+}
+
+// a calibration (sensors of rows x cols, or sphere-only with rows = 0), a frame on it, the frame's plane buffers and
+// its sensor pyramid; n_*: the fallible calls each creation is known to make at these sizes
+static void handles(int rows, int cols, int sph_rows, int sph_cols, int n_calib, int n_frame) {
+    r360_ctx ctx{};
+    r360_calib* const no_calib = (r360_calib*)0x10;
+    r360_frame* const no_frame = (r360_frame*)0x20;
+    r360_calib* cal = nullptr;
+    r360_frame* f = nullptr;
+    const int nc = fail_each(
+        [&] {
+            r360_calib* c = no_calib;
+            const int rc = calib_new(&ctx, rows, cols, sph_rows, sph_cols, &c);
+            if (rc) CHECK(c == no_calib); else cal = c;   // *out untouched on failure
+            return rc;
+        },
+        [&] { delete cal; cal = nullptr; });
+    CHECK(nc == n_calib);
+    CHECK(calib_new(&ctx, rows, cols, sph_rows, sph_cols, &cal) == 0);
+    CHECK(cal->n_levels == 1 && cal->trig[0].sinphi && cal->trig[0].costh && !cal->trig[1].sinphi);
+    CHECK(!cal->d_rt == !rows && !cal->d_rt_inv == !rows && !cal->d_st_costh == !rows);
+    const int sr = cal->sph_rows, sc = cal->sph_cols;
+    CHECK(sr == (rows ? 5 : sph_rows) && sc == (rows ? 32 : sph_cols));
+
+    const int nf = fail_each(
+        [&] {
+            r360_frame* g = no_frame;
+            const int rc = frame_new(&ctx, cal, &g);
+            if (rc) CHECK(g == no_frame); else f = g;
+            return rc;
+        },
+        [&] { delete f; f = nullptr; });
+    CHECK(nf == n_frame);
+    fresh();
+    CHECK(frame_new(&ctx, cal, &f) == 0);
+    {   // the allocations of a frame, in order: sensor images, sphere images, the one level, counters and the level table
+        const size_t ns = (size_t)8 * rows * cols, nsph = (size_t)sr * sc;
+        std::vector<size_t> want;
+        if (ns) want = {ns * 3, ns * 2, ns * 4};
+        for (size_t b : {nsph * 3, nsph * 2, nsph * sizeof(float2), nsph * sizeof(float4), nsph * sizeof(float4), nsph * 4,
+                         sizeof(int) * R360_MAX_PYR, sizeof(int) * R360_MAX_PYR * 1, sizeof(SrcLevel) * R360_MAX_PYR})
+            want.push_back(b);
+        CHECK(g_sizes == want);
+        CHECK(f->lv[0].p0 && f->lv[0].pk && !f->lv[1].p0 && f->d_npts && f->bgr_ev && !f->d_bgr == !rows);
+    }
+    if (rows) {
+        const int np = fail_each(
+            [&] {
+                const int rc = f->pl.alloc(f->rows, f->cols);
+                // a failure leaves no partial set behind for the next call to take for complete
+                if (rc) CHECK(!f->pl.v.cloud && !f->pl.v.h_nmodels && !f->pl.done && !f->pl.ready && f->pl.mem.dev.empty());
+                else CHECK(f->pl.v.cloud && f->pl.v.h_nmodels && f->pl.done && f->pl.ready && f->pl.alloc(f->rows, f->cols) == 0);
+                return rc;
+            },
+            [&] { f->pl.release(); });
+        CHECK(np == 41);   // 35 device buffers, 4 pinned ones, 2 events
+        CHECK(f->pl.alloc(f->rows, f->cols) == 0);
+        CHECK(f->pl.w == cols / 2 && f->pl.h == rows / 2 && f->pl.v.contour_cap == 2L * 8 * f->pl.w * f->pl.h);
+        { const PlaneDev view = f->pl.v; (void)view; }   // a view: copied, and the copy frees nothing
+        f->pl.release();
+        // one lazily allocated sensor-pyramid level (4 x 8 is below the halving limit): each drop starts a new frame
+        const int nsp = fail_each(
+            [&] {
+                const int rc = f->alloc_sensor_pyramid();
+                if (rc) CHECK(f->n_slevels == 0 && !f->sp[0].p0 && !f->sp[0].tg && f->sp_mem.dev.empty());
+                else CHECK(f->n_slevels == 1 && f->sp[0].p0 && f->sp[0].tg && !f->sp[1].p0 && f->alloc_sensor_pyramid() == 0);
+                return rc;
+            },
+            [&] {
+                delete f;
+                f = nullptr;
+                CHECK(frame_new(&ctx, cal, &f) == 0);
+            });
+        CHECK(nsp == 2);
+        CHECK(f->alloc_sensor_pyramid() == 0 && f->pl.alloc(f->rows, f->cols) == 0);
+        // the CLAMS tables are replaced release first: free, then malloc, then the blocking copy
+        std::vector<float> mult(24, 1.f), counts(24, 2.f);
+        CHECK(cal->upload_clams(mult, counts) == 0);
+        fresh();
+        CHECK(cal->upload_clams(mult, counts) == 0 && log_str() == "free malloc memcpy free malloc memcpy");
+        fresh();
+        g_fail_call = 3;   // the second table's allocation fails: no dangling view
+        CHECK(cal->upload_clams(mult, counts) == -1 && cal->clams.d_mult && !cal->clams.d_counts);
+    }
+    delete f;      // frame with everything: plane buffers, sensor pyramid, event
+    delete cal;
+    CHECK(g_live.empty() && g_events.empty());
+}
+
 int main() {
+    handles(4, 8, 0, 0, 20, 15);    // sensors of 4 x 8: a sphere of 5 x 32, one level
+    handles(0, 0, 2, 8, 8, 12);     // sphere-only, 2 x 8
     basic<DevBuf<double>>("malloc", "free");
     basic<PinnedBuf<double>>("hostmalloc", "hostfree");
     zeroed();

@@ -5,8 +5,10 @@ calibration's handles through DevBuf / PinnedBuf, rgbd360_amd/csrc/host/devmem.h
 the growth rules of its buffers (the 1024-item floors of the voxel grid and GICP, the map's half-as-much-again step,
 the per-graph and per-row sizes of the pose graph and the rig calibration, one chunk more than R360_TOPO_CHUNK, the
 per-pixel occlusion buffers and deferred queues, the batch set) and compares every result bit for bit (_cases.same)
-with the same call on a fresh context or handle.  The last case creates and destroys contexts that ran an occlusion
-alignment.  Nothing here makes an allocation fail: those paths are tests/test_devmem_host.py's."""
+with the same call on a fresh context or handle.  One case creates and destroys contexts that ran an occlusion
+alignment.  The last two do the same with the handles whose buffers are sized once: calibrations and frames of two
+sensor sizes, fully built, created and destroyed in turn and with overlapping lifetimes.  Nothing here makes an
+allocation fail: those paths are tests/test_devmem_host.py's."""
 import contextlib
 
 import numpy as np
@@ -18,7 +20,7 @@ import _gicp_cases as GC
 import _pgo_cases as PC
 import _rigcal_cases as RC
 import _topo_cases as TC
-from _cases import noise_sphere, same
+from _cases import PLANE_SEEDS, PLANE_SHAPES, noise_sphere, same, sensor_levels
 from test_gpu_voxel import _check_against_model
 
 pytestmark = pytest.mark.gpu
@@ -267,3 +269,94 @@ def test_context_churn():
         with context() as ctx:
             runs.append(_align(ctx, "64x384", 1))
     _same_all(runs[0], runs[7], "context churn")
+
+
+# ------------------------------------------------------------------ calibrations and frames
+FRAME_SHAPES = [(66, 90), (32, 162)]
+assert set(FRAME_SHAPES) <= set(PLANE_SHAPES)
+FULL_BUILD = (R.BUILD_UNDISTORT | R.BUILD_SPHERE | R.BUILD_PYRAMID | R.BUILD_SENSOR_PYRAMID | R.BUILD_CLOUD |
+              R.BUILD_PLANES)
+_IMAGES = {}
+
+
+def _images(cal, shape, seed):
+    """The synthetic room's 8 sensor images at `shape`, rendered once (on the host) and left unchanged."""
+    if (shape, seed) not in _IMAGES:
+        _IMAGES[shape, seed] = cal.synth_frame(seed, R.synth_path_pose(seed, 0))
+    return _IMAGES[shape, seed]
+
+
+def _sphere_levels(rows, cols):
+    n = 0
+    while n < 6 and rows >= 2 and cols >= 8 and cols % 4 == 0:
+        n += 1
+        if rows % 2 or cols % 2:
+            break
+        rows, cols = rows // 2, cols // 2
+    return n
+
+
+def _built_frame(ctx, shape, seed=PLANE_SEEDS[0]):
+    """Calibration and frame created, images uploaded, everything built: sphere, pyramid, sensor pyramid, planes."""
+    cal = R.Calib360(ctx, *shape)
+    cal.loadExtrinsicCalibration(R.EXTRINSICS_DIR)
+    f = R.Frame360(cal)
+    f.upload(*_images(cal, shape, seed))
+    f.build(FULL_BUILD)
+    return cal, f
+
+
+def _read_back(f, shape):
+    """The sphere's level images, the sensors' (sensors 0 and 7), the sensors' clouds, the labels, the regions and the
+    planes, as arrays."""
+    n = _sphere_levels(f.sph_rows, f.sph_cols)
+    assert n >= 2
+    out = list(f.sphere())
+    for l in range(n):
+        out += list(f.level(l).values())
+    for l in range(len(sensor_levels(*shape))):
+        for k in (0, 7):
+            out += list(f.sensor_level(k, l).values())
+    out += list(f.cloud()) + list(f.labels())
+    # (at these sizes a sensor's cloud has few labels above the 80-point bar, and may have no region at all)
+    for d in [r for k in range(8) for r in f.regions(k)] + f.planes():
+        out += [np.asarray(d[key]) for key in sorted(d)]
+    return out
+
+
+def _drop(cal, f):
+    f.close()
+    cal.close()
+
+
+def test_frame_churn():
+    """Eight times at each of two sensor sizes: calibration and frame created, uploaded, fully built, read back,
+    destroyed.  The eighth read-back is the first, bit for bit."""
+    with context() as ctx:
+        for shape in FRAME_SHAPES:
+            runs = []
+            for _ in range(8):
+                cal, f = _built_frame(ctx, shape)
+                runs.append(_read_back(f, shape))
+                _drop(cal, f)
+            _same_all(runs[0], runs[7], f"frame churn at {shape}")
+
+
+def test_frames_with_overlapping_lifetimes():
+    """A and B built, A destroyed, C created and built at the other size where A's memory was: B reads back as before,
+    and C as on a fresh context."""
+    small, wide = FRAME_SHAPES
+    with context() as ctx:
+        cal_a, a = _built_frame(ctx, small)
+        cal_b, b = _built_frame(ctx, small, PLANE_SEEDS[1])
+        before = _read_back(b, small)
+        _drop(cal_a, a)
+        cal_c, c = _built_frame(ctx, wide)
+        got = _read_back(c, wide)
+        _same_all(before, _read_back(b, small), "B after A went and C came")
+        _drop(cal_b, b)
+        _drop(cal_c, c)
+    with context() as fresh:
+        cal_c, c = _built_frame(fresh, wide)
+        _same_all(got, _read_back(c, wide), "C against a fresh context")
+        _drop(cal_c, c)
