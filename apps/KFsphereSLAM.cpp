@@ -30,8 +30,13 @@
 // (r360::GlobalMap360::removeOutliers: pcl::StatisticalOutlierRemoval with meanK K, multiplier MUL and a search bound of
 // D m, 0.5 by default, or pcl::RadiusOutlierRemoval) and prints one more line, "map cleaned: <before> -> <after> points
 // (<short> short)"; without the flag the output is what it was.
+// --map-normals K,R estimates the final map's normals and curvature where it lies (r360::GlobalMap360::estimateNormals:
+// pcl::NormalEstimation over at most K points within R m, turned towards the nearest optimised keyframe position), after
+// --clean-map if given, and prints one more line, "map normals: <points> points, <short> short, <mean> neighbours on
+// average".  --save-map file.pcd writes the final map (binary), with its normals when they were estimated.
 //   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]
 //                       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]
+//                       [--map-normals K,R] [--save-map file.pcd]
 //          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
 //          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
 #include <rgbd360/rgbd360.h>
@@ -76,6 +81,10 @@ int main(int argc, char** argv) {
     bool clean_map = false;                              // --clean-map
     r360_outlier_params clean;
     r360_outlier_default_params(&clean);
+    bool map_normals = false;                            // --map-normals
+    r360_normal_params normal_prm;
+    r360_normal_default_params(&normal_prm);
+    std::string save_map;                                // --save-map
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
         if (a == "--clean-map" && k + 1 < argc) {
@@ -110,6 +119,11 @@ int main(int argc, char** argv) {
         else if (a == "--min-gap" && k + 1 < argc) min_gap = std::atoi(argv[++k]);
         else if (a == "--kf-dist" && k + 1 < argc) kf_dist = float(std::atof(argv[++k]));
         else if (a == "--save" && k + 1 < argc) save = argv[++k];
+        else if (a == "--save-map" && k + 1 < argc) save_map = argv[++k];
+        else if (a == "--map-normals" && k + 1 < argc) {
+            map_normals = true;
+            bad_arg = bad_arg || std::sscanf(argv[++k], "%d,%f", &normal_prm.k, &normal_prm.radius) != 2;
+        }
         else if (a == "--submaps") submaps = true;
         else if (a == "--synthetic-frames" && k + 1 < argc) { frames_arg = argv[++k]; synthetic = true; }
         else if (a == "--synthetic" && k + 1 < argc) { n_synth = std::atoi(argv[++k]); synthetic = true; }
@@ -127,6 +141,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
                              "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n"
                              "       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]\n"
+                             "       [--map-normals K,R] [--save-map file.pcd]\n"
                              "  --robust       loop edges get the kernel, of width D on sqrt(chi2); chain and PbMap edges stay quadratic\n"
                              "  --reject-chi2  after each optimisation loop edges with chi2 > T are deactivated and the graph is optimised again\n"
                              "  --false-loop   when keyframe J is added, also add a wrong loop edge I -> J (demonstration)\n"
@@ -134,7 +149,10 @@ int main(int argc, char** argv) {
                              "  (--reject-chi2 inf prints and rejects nothing).  The dense Hessians are not calibrated information\n"
                              "  matrices, so chi2 has no unit scale: choose D and T from these printed values.\n"
                              "  --clean-map    the final map at the optimised poses through the statistical (sor:meanK,multiplier[,bound in m])\n"
-                             "                 or the radius (radius:R in m,min neighbours) outlier filter, on the GPU\n", argv[0]);
+                             "                 or the radius (radius:R in m,min neighbours) outlier filter, on the GPU\n"
+                             "  --map-normals  normals and curvature of the final map from at most K points within R m, turned towards the\n"
+                             "                 nearest keyframe position, on the GPU (after --clean-map)\n"
+                             "  --save-map     the final map as a binary PCD file, with the normals when they were estimated\n", argv[0]);
         return 1;
     }
     const bool edge_report = robust_kind != R360_GRAPH_KERNEL_NONE || reject_chi2 >= 0.0 || false_from >= 0;
@@ -406,6 +424,25 @@ int main(int argc, char** argv) {
             r360_outlier_stats st;
             map.removeOutliers(clean, &st);
             std::printf("map cleaned: %zu -> %zu points (%zu short)\n", sizes[1], map.size(), st.n_short);
+        }
+        if (map_normals) {   // the viewpoints: where the keyframes stood, at the optimised poses
+            std::vector<float> views;
+            for (size_t k = 0; k < kfs.size(); ++k)
+                for (int r = 0; r < 3; ++r) views.push_back(vOptimizedPoses[k](r, 3));
+            r360_normal_stats st;
+            map.estimateNormals(normal_prm, views, &st);
+            std::printf("map normals: %zu points, %zu short, %.3f neighbours on average\n", st.n_in, st.n_short,
+                        st.n_finite ? double(st.sum_neighbors) / double(st.n_finite) : 0.0);
+        }
+        if (!save_map.empty()) {
+            if (map_normals) {
+                map.savePCDNormals(save_map, 1);
+            } else {
+                r360::PointCloud cloud;
+                map.download(cloud);
+                if (r360_pcd_write(save_map.c_str(), cloud.xyz.data(), cloud.rgba.data(), int(cloud.size()), 1, 1))
+                    throw std::runtime_error("cannot write " + save_map);
+            }
         }
         if (!save.empty()) optimizer.saveGraph(save);
     } catch (const std::exception& e) {

@@ -37,6 +37,7 @@ using r360::FilterPointCloud;
 using r360::GeneralizedIterativeClosestPoint;
 using r360::Frame360;
 using r360::GraphOptimizer;
+using r360::NormalEstimation;
 using r360::PbMap;
 using r360::Plane;
 using r360::RegisterPhotoICP;

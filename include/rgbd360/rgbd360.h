@@ -221,6 +221,19 @@ struct PointCloud {
     }
 };
 
+// Normals and curvature of a cloud, row for row (the normal_x / normal_y / normal_z / curvature of
+// pcl::PointCloud<pcl::Normal>): NaN where the point was dropped or had fewer than three neighbours.
+struct PointCloudNormal {
+    std::vector<float> normals;         // [size][3]
+    std::vector<float> curvature;       // [size]
+    size_t size() const { return curvature.size(); }
+    bool empty() const { return curvature.empty(); }
+    void resize(size_t n) {
+        normals.resize(3 * n);
+        curvature.resize(n);
+    }
+};
+
 class Context {
   public:
     explicit Context(int device = 0) { check(r360_ctx_create(device, &h_), "r360_ctx_create"); }
@@ -877,6 +890,31 @@ class GlobalMap360 {
     void removeOutliers(const r360_outlier_params& params, r360_outlier_stats* stats = nullptr) {
         check(r360_ctx_map_filter_outliers(ctx_->get(), &params, stats), "GlobalMap360::removeOutliers");
     }
+    // normals and curvature of the map where it lies (r360_ctx_map_estimate_normals), each turned towards the nearest
+    // of `viewpoints` (xyz triples: the keyframe positions); they stay on the GPU, valid until the map next changes
+    void estimateNormals(const r360_normal_params& params, const std::vector<float>& viewpoints,
+                         r360_normal_stats* stats = nullptr) {
+        check(r360_ctx_map_estimate_normals(ctx_->get(), &params, viewpoints.data(), int(viewpoints.size() / 3), stats),
+              "GlobalMap360::estimateNormals");
+    }
+    // the map's normals in the order of download(); throws when the map changed since estimateNormals
+    void getNormals(PointCloudNormal& out) const {
+        size_t n = 0;
+        check(r360_ctx_map_download_normals(ctx_->get(), nullptr, nullptr, 0, &n), "GlobalMap360::getNormals");
+        out.resize(n);
+        check(r360_ctx_map_download_normals(ctx_->get(), out.normals.data(), out.curvature.data(), n, &n),
+              "GlobalMap360::getNormals");
+    }
+    // the map with its normals as a PointXYZRGBNormal file (r360_pcd_write_normals; mode as r360_pcd_write)
+    void savePCDNormals(const std::string& path, int mode = 0) const {
+        PointCloud cloud;
+        PointCloudNormal nrm;
+        download(cloud);
+        getNormals(nrm);
+        check(r360_pcd_write_normals(path.c_str(), cloud.xyz.data(), cloud.rgba.data(), nrm.normals.data(),
+                                     nrm.curvature.data(), cloud.size(), mode),
+              "GlobalMap360::savePCDNormals");
+    }
   private:
     std::shared_ptr<Context> keep_;
     Context* ctx_;
@@ -886,6 +924,46 @@ inline bool GlobalMap360::add(Frame360& keyframe, const Matrix4f& pose) {
     return check(r360_ctx_map_add_frame(ctx_->get(), keyframe.get(), pose.data(), -2.0f, 1.0f, box_, voxel_),
                  "GlobalMap360::add") == 0;
 }
+
+// pcl::NormalEstimation with PCL's names, on the GPU of the calling thread's default context or of the Context given
+// (r360_cloud_normals).  The neighbourhood is at most k points within a radius: setKSearch alone
+// searches within setSearchBound (0.5 m by default), setRadiusSearch alone takes at most 64 points, and both together
+// give the library's rule.  setViewPoint / setViewPoints: the normals turn towards the nearest viewpoint.  The input
+// cloud is referenced, not copied: it must outlive compute().
+class NormalEstimation {
+  public:
+    NormalEstimation() {}
+    explicit NormalEstimation(Context& ctx) : ctx_(&ctx) {}
+    void setInputCloud(const PointCloud& cloud) { cloud_ = &cloud; }
+    void setKSearch(int k) { k_ = k; }
+    void setRadiusSearch(double radius) { radius_ = float(radius); }
+    void setSearchBound(double bound) { bound_ = float(bound); }
+    void setViewPoint(float x, float y, float z) { views_.assign({x, y, z}); }
+    void setViewPoints(const std::vector<float>& xyz) { views_ = xyz; }
+    void getViewPoint(float& x, float& y, float& z) const { x = views_[0]; y = views_[1]; z = views_[2]; }
+    const r360_normal_stats& stats() const { return stats_; }
+    void compute(PointCloudNormal& out) {
+        if (!cloud_) throw std::invalid_argument("NormalEstimation::compute: no input cloud");
+        r360_normal_params p;
+        r360_normal_default_params(&p);
+        if (k_ > 0 || radius_ > 0.f) {
+            p.k = k_ > 0 ? k_ : 64;
+            p.radius = radius_ > 0.f ? radius_ : bound_;
+        }
+        Context& c = ctx_ ? *ctx_ : default_context();
+        out.resize(cloud_->size());
+        check(r360_cloud_normals(c.get(), cloud_->xyz.data(), cloud_->size(), &p, views_.data(), int(views_.size() / 3),
+                                 out.normals.data(), out.curvature.data(), &stats_),
+              "NormalEstimation::compute");
+    }
+  private:
+    Context* ctx_ = nullptr;
+    const PointCloud* cloud_ = nullptr;
+    int k_ = 0;
+    float radius_ = 0.f, bound_ = 0.5f;
+    std::vector<float> views_ = {0.f, 0.f, 0.f};
+    r360_normal_stats stats_ = {0, 0, 0, 0};
+};
 
 // ------------------------------------------------------------------ Generalized-ICP
 // pcl::GeneralizedIterativeClosestPoint with the call surface of Registration/RegisterPairRGBD360.cpp:109-149, on the

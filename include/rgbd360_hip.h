@@ -775,6 +775,56 @@ int r360_ctx_map_filter_outliers(r360_ctx* ctx, const r360_outlier_params* param
 int r360_cloud_outlier_eval(r360_ctx* ctx, const float* xyz, size_t n, const r360_outlier_params* params, double* score,
                             int* count);
 
+/* ---------------------------------------------------------------- surface normals and curvature
+ * pcl::NormalEstimation, restated from PCL 1.7 features/normal_3d.h (unpinned), for a host cloud and for the context's
+ * global map where it lies.  The statement is tests/normal_model.py and DESIGN.md §5b-3.
+ * A row with a non-finite coordinate is dropped: its normal and curvature are NaN and it is nobody's neighbour.  The
+ * neighbourhood of point i is i itself, then its nearest other points with squared distance <= (double)radius squared,
+ * at most k points in all (k = 3..64), in ascending (squared distance, input index) order; the squared distance is that
+ * of the outlier filters.  One rule covers both PCL modes: a radius beyond the cloud's diameter is setKSearch(k), and
+ * k = 64 is setRadiusSearch(radius) for every point with at most 63 others within it.  Unlike PCL the search is always
+ * bounded, the neighbourhood is capped at 64, ties go to the lower index, and the moments are fp64 two-pass sums.
+ * A point with m < 3 neighbours is short: normal and curvature NaN.  Otherwise mean = (sum p_j) / m and
+ * C = sum (p_j - mean)(p_j - mean)^T / m, summed in neighbourhood order in double; l0 <= l1 <= l2 the eigenvalues of C;
+ * the normal is the unit eigenvector of l0 and curvature = |l0| / (l0 + l1 + l2), 0 when the trace is 0.
+ * Orientation (flipNormalTowardsViewpoint): v = the nearest of the n_view viewpoints ([n_view][3], n_view = 1..4096) by
+ * squared distance in double, ties to the lower index; the normal is negated iff (v - p) . n < 0 in double.  One
+ * viewpoint is PCL's case; the keyframe positions serve a map fused from many keyframes.
+ * Outputs are the float32 of the double values; two runs give the same bytes.
+ * Defaults: k 20, radius 0.25 m (five leaves of the reference's 5 cm voxel): starting values, no claim about a dataset.
+ * Checks (no GPU needed): ctx or params NULL, k outside 3..64, radius not positive and finite, n_view outside 1..4096,
+ * viewpoints NULL, n > 2^30: R360_EINVAL (-2).
+ * stats: n_in rows given, n_finite of them finite, n_short short points, sum_neighbors = the sum of m over the finite
+ * rows (the point itself counts).
+ * r360_cloud_normals: normals [n][3], curvature [n]; either and stats may be NULL.
+ * r360_ctx_map_estimate_normals: the normals of the context's map, kept on the device in the map's order until the map
+ * next changes (r360_ctx_map_reset, _add_cloud, _add_frame, _filter_outliers).  An empty map gives 0 and zero stats; an
+ * error leaves the map and its normals as they were.
+ * r360_ctx_map_download_normals: an error (< 0) when the map has no valid normals; *n is the map's size either way;
+ * cap < *n is an error (< 0); normals and curvature NULL: only *n.
+ * r360_cloud_normals_eval (parity hook): knn [n][k] the neighbourhood's input indices in its order, the point itself
+ * first, -1 padded; count [n] m, -1 for a dropped row; normal [n][3], eig [n][3] (ascending) and curvature [n] in
+ * double, NaN for dropped and short rows.  Any pointer may be NULL.
+ * r360_pcd_write_normals / _read_normals: a PointXYZRGBNormal cloud, FIELDS x y z rgba normal_x normal_y normal_z
+ * curvature, WIDTH n HEIGHT 1, in r360_pcd_write's modes (ascii prints the normals with nine digits, which return the
+ * bits).  rgba, normals, curvature may be NULL (written as 0 / read and dropped); read fails on a file without the
+ * normal fields when it is asked for them; cap < *n reads the first cap points. */
+typedef struct { int k; float radius; } r360_normal_params;
+typedef struct { size_t n_in, n_finite, n_short; unsigned long long sum_neighbors; } r360_normal_stats;
+void r360_normal_default_params(r360_normal_params* params);
+int r360_cloud_normals(r360_ctx* ctx, const float* xyz, size_t n, const r360_normal_params* params,
+                       const float* viewpoints, int n_view, float* normals, float* curvature, r360_normal_stats* stats);
+int r360_ctx_map_estimate_normals(r360_ctx* ctx, const r360_normal_params* params, const float* viewpoints, int n_view,
+                                  r360_normal_stats* stats);
+int r360_ctx_map_download_normals(r360_ctx* ctx, float* normals, float* curvature, size_t cap, size_t* n);
+int r360_cloud_normals_eval(r360_ctx* ctx, const float* xyz, size_t n, const r360_normal_params* params,
+                            const float* viewpoints, int n_view, int* knn, int* count, double* normal, double* eig,
+                            double* curvature);
+int r360_pcd_write_normals(const char* path, const float* xyz, const uint32_t* rgba, const float* normals,
+                           const float* curvature, size_t n, int mode);
+int r360_pcd_read_normals(const char* path, float* xyz, uint32_t* rgba, float* normals, float* curvature, size_t cap,
+                          size_t* n);
+
 /* ---------------------------------------------------------------- Generalized-ICP
  * pcl::GeneralizedIterativeClosestPoint as Registration/RegisterPairRGBD360.cpp:109-149 calls it, restated (PCL is
  * not pinned): the statement is tests/gicp_model.py and DESIGN.md §5c.  Per cloud: rows with a non-finite coordinate

@@ -120,6 +120,30 @@ class OutlierStats(C.Structure):
     ]
 
 
+class NormalParams(C.Structure):
+    """r360_normal_params — pcl::NormalEstimation's neighbourhood: at most k points, the point itself included, within
+    radius (see include/rgbd360_hip.h)."""
+    _fields_ = [("k", C.c_int), ("radius", C.c_float)]
+
+    @classmethod
+    def default(cls) -> "NormalParams":
+        p = cls()
+        lib().r360_normal_default_params(C.byref(p))
+        return p
+
+    @classmethod
+    def make(cls, k: int = 20, radius: float = 0.25) -> "NormalParams":
+        p = cls.default()
+        p.k, p.radius = k, radius
+        return p
+
+
+class NormalStats(C.Structure):
+    """r360_normal_stats — what one normal estimation saw."""
+    _fields_ = [("n_in", C.c_size_t), ("n_finite", C.c_size_t), ("n_short", C.c_size_t),
+                ("sum_neighbors", C.c_ulonglong)]
+
+
 class GraphParams(C.Structure):
     """r360_graph_params — pose-graph optimisation settings (see include/rgbd360_hip.h)."""
     _fields_ = [
@@ -471,6 +495,15 @@ _SIGS = [
                                              C.POINTER(C.c_size_t), C.POINTER(OutlierStats)]),
     ("r360_ctx_map_filter_outliers", C.c_int, [_P, C.POINTER(OutlierParams), C.POINTER(OutlierStats)]),
     ("r360_cloud_outlier_eval", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(OutlierParams), _DP, _IP]),
+    ("r360_normal_default_params", None, [C.POINTER(NormalParams)]),
+    ("r360_cloud_normals", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(NormalParams), _FP, C.c_int, _FP, _FP,
+                                     C.POINTER(NormalStats)]),
+    ("r360_ctx_map_estimate_normals", C.c_int, [_P, C.POINTER(NormalParams), _FP, C.c_int, C.POINTER(NormalStats)]),
+    ("r360_ctx_map_download_normals", C.c_int, [_P, _FP, _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_cloud_normals_eval", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(NormalParams), _FP, C.c_int, _IP, _IP, _DP, _DP,
+                                          _DP]),
+    ("r360_pcd_write_normals", C.c_int, [C.c_char_p, _FP, _P, _FP, _FP, C.c_size_t, C.c_int]),
+    ("r360_pcd_read_normals", C.c_int, [C.c_char_p, _FP, _P, _FP, _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r360_gicp_default_params", None, [C.POINTER(GicpParams)]),
     ("r360_gicp_set_source", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
     ("r360_gicp_set_target", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
@@ -590,6 +623,29 @@ def pcd_read(path: str):
     _check(lib().r360_pcd_read(path.encode(), _fptr(xyz), _vptr(rgba), n.value, C.byref(n), C.byref(w), C.byref(h)),
            "pcd_read")
     return xyz, rgba, w.value, h.value
+
+
+def pcd_write_normals(path: str, xyz, rgba, normals, curvature, mode: int = PCD_ASCII):
+    """A PointXYZRGBNormal cloud (x y z rgba normal_x normal_y normal_z curvature), unorganised, in pcd_write's modes."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    rgba = None if rgba is None else np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    curvature = np.ascontiguousarray(curvature, np.float32).reshape(-1)
+    assert normals.shape[0] == n and curvature.shape[0] == n and (rgba is None or rgba.shape[0] == n)
+    _check(lib().r360_pcd_write_normals(path.encode(), _fptr(xyz), None if rgba is None else _vptr(rgba), _fptr(normals),
+                                        _fptr(curvature), n, mode), "pcd_write_normals")
+
+
+def pcd_read_normals(path: str):
+    """(xyz [n,3] f32, rgba [n] u32, normals [n,3] f32, curvature [n] f32) of a PCD file that holds the normal fields."""
+    n = C.c_size_t()
+    _check(lib().r360_pcd_read_normals(path.encode(), None, None, None, None, 0, C.byref(n)), "pcd_read_normals")
+    xyz, rgba = np.zeros((n.value, 3), np.float32), np.zeros(n.value, np.uint32)
+    nrm, curv = np.zeros((n.value, 3), np.float32), np.zeros(n.value, np.float32)
+    _check(lib().r360_pcd_read_normals(path.encode(), _fptr(xyz), _vptr(rgba), _fptr(nrm), _fptr(curv), n.value, C.byref(n)),
+           "pcd_read_normals")
+    return xyz, rgba, nrm, curv
 
 
 def _fptr(a: np.ndarray):
@@ -761,6 +817,54 @@ class Context:
             _check(lib().r360_cloud_outlier_eval(self.h, _fptr(xyz), n, C.byref(params), None, out.ctypes.data_as(_IP)),
                    "outlier_eval")
         return out
+
+    @staticmethod
+    def _viewpoints(viewpoints) -> np.ndarray:
+        return np.ascontiguousarray(viewpoints, np.float32).reshape(-1, 3)
+
+    def estimate_normals(self, xyz, viewpoints=(0.0, 0.0, 0.0), params: "NormalParams | None" = None):
+        """pcl::NormalEstimation on this context's GPU (r360_cloud_normals): per point the unit normal of its at most k
+        nearest points within the radius, turned towards the nearest of `viewpoints` ([v,3] or one point), and the
+        curvature; NaN for dropped and short rows.  Returns (normals [n,3] f32, curvature [n] f32, NormalStats)."""
+        xyz, _ = _cloud_arrays(xyz, None)
+        p = params if params is not None else NormalParams.default()
+        v = self._viewpoints(viewpoints)
+        n = xyz.shape[0]
+        nrm, curv, st = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), NormalStats()
+        _check(lib().r360_cloud_normals(self.h, _fptr(xyz), n, C.byref(p), _fptr(v), v.shape[0], _fptr(nrm), _fptr(curv),
+                                        C.byref(st)), "estimate_normals")
+        return nrm, curv, st
+
+    def map_estimate_normals(self, viewpoints=(0.0, 0.0, 0.0), params: "NormalParams | None" = None) -> "NormalStats":
+        """The same on the context's global map where it lies; the normals stay in HBM, valid until the map changes."""
+        p = params if params is not None else NormalParams.default()
+        v = self._viewpoints(viewpoints)
+        st = NormalStats()
+        _check(lib().r360_ctx_map_estimate_normals(self.h, C.byref(p), _fptr(v), v.shape[0], C.byref(st)),
+               "map_estimate_normals")
+        return st
+
+    def map_normals(self):
+        """The map's normals and curvature (normals [n,3] f32, curvature [n] f32) in the map's order; raises when the
+        map changed since they were estimated."""
+        n = C.c_size_t()
+        _check(lib().r360_ctx_map_download_normals(self.h, None, None, 0, C.byref(n)), "map_normals")
+        nrm, curv = np.zeros((n.value, 3), np.float32), np.zeros(n.value, np.float32)
+        _check(lib().r360_ctx_map_download_normals(self.h, _fptr(nrm), _fptr(curv), n.value, C.byref(n)), "map_normals")
+        return nrm, curv
+
+    def normals_eval(self, xyz, viewpoints, params: "NormalParams"):
+        """Parity hook (r360_cloud_normals_eval): (knn [n,k] i32, count [n] i32, normal [n,3] f64, eig [n,3] f64,
+        curvature [n] f64)."""
+        xyz, _ = _cloud_arrays(xyz, None)
+        v = self._viewpoints(viewpoints)
+        n = xyz.shape[0]
+        knn, count = np.full((n, params.k), -1, np.int32), np.full(n, -1, np.int32)
+        nrm, eig, curv = np.full((n, 3), np.nan), np.full((n, 3), np.nan), np.full(n, np.nan)
+        _check(lib().r360_cloud_normals_eval(self.h, _fptr(xyz), n, C.byref(params), _fptr(v), v.shape[0],
+                                             knn.ctypes.data_as(_IP), count.ctypes.data_as(_IP), _dptr(nrm), _dptr(eig),
+                                             _dptr(curv)), "normals_eval")
+        return knn, count, nrm, eig, curv
 
     def _gicp_set(self, fn, xyz, params, what):
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)

@@ -384,9 +384,10 @@ extern "C" int r360_pcd_write(const char* path, const float* xyz, const uint32_t
 }
 
 // Reads a .pcd into xyz [cap][3] / rgba [cap] (either may be NULL; a cloud without an rgb/rgba
-// field reads as 0).  *n = points in the file, *width / *height as in its header.
-extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_t cap, size_t* n_out, int* width,
-                             int* height) {
+// field reads as 0).  *n = points in the file, *width / *height as in its header.  want_normals: the file must hold
+// normal_x / normal_y / normal_z / curvature, which go to nrm [cap][3] / curv [cap] (either may be NULL).
+static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* nrm, float* curv, bool want_normals,
+                           size_t cap, size_t* n_out, int* width, int* height) {
     if (!path) { r360_set_error("null path"); return -2; }
     std::ifstream f(path, std::ios::binary);
     if (!f) { r360_set_error("cannot open %s", path); return -1; }
@@ -418,6 +419,7 @@ extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_
     if (N < 0) N = W * H;
     if (N != W * H) { r360_set_error("%s: POINTS %ld != WIDTH*HEIGHT %ld", path, N, W * H); return -1; }
     int ix = -1, iy = -1, iz = -1, ic = -1;
+    int in[4] = {-1, -1, -1, -1};   // normal_x, normal_y, normal_z, curvature
     std::vector<size_t> foff(F.size());
     size_t rec = 0;
     for (size_t k = 0; k < F.size(); ++k) {
@@ -431,8 +433,15 @@ extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_
         rec += (size_t)p.size * p.count;
         if (p.name == "x") ix = (int)k; else if (p.name == "y") iy = (int)k; else if (p.name == "z") iz = (int)k;
         else if (p.name == "rgba" || p.name == "rgb") ic = (int)k;
+        else if (p.name == "normal_x") in[0] = (int)k; else if (p.name == "normal_y") in[1] = (int)k;
+        else if (p.name == "normal_z") in[2] = (int)k; else if (p.name == "curvature") in[3] = (int)k;
     }
     if (ix < 0 || iy < 0 || iz < 0) { r360_set_error("%s: no x/y/z fields", path); return -1; }
+    if (want_normals && (in[0] < 0 || in[1] < 0 || in[2] < 0 || in[3] < 0)) {
+        r360_set_error("%s: no normal_x/normal_y/normal_z/curvature fields", path);
+        return -1;
+    }
+    const bool normals = want_normals && (nrm || curv);
     const size_t n = (size_t)N;
     if (n_out) *n_out = n;
     if (width) *width = (int)W;
@@ -442,6 +451,11 @@ extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_
         if (i >= m) return;
         if (xyz) for (int k = 0; k < 3; ++k) xyz[3 * i + k] = (float)v[k];
         if (rgba) rgba[i] = c;
+    };
+    auto store_normal = [&](size_t i, const float* w) {
+        if (i >= m) return;
+        if (nrm) for (int k = 0; k < 3; ++k) nrm[3 * i + k] = w[k];
+        if (curv) curv[i] = w[3];
     };
     auto color_bits = [&](const uint8_t* p) -> uint32_t {
         if (ic < 0) return 0;
@@ -460,10 +474,13 @@ extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_
             for (size_t t = 0; t < ntok; ++t)
                 if (!(ts >> toks[t])) { r360_set_error("%s: truncated ascii data at point %zu", path, i); return -1; }
             double v[3];
+            float w[4] = {0.f, 0.f, 0.f, 0.f};
             uint32_t c = 0;
             size_t t = 0;
             for (size_t k = 0; k < F.size(); ++k) {
                 const std::string& s = toks[t];
+                for (int q = 0; q < 4; ++q)
+                    if (normals && (int)k == in[q]) w[q] = (s == "nan" || s == "NaN") ? NAN : strtof(s.c_str(), nullptr);
                 if ((int)k == ix || (int)k == iy || (int)k == iz)
                     v[(int)k == ix ? 0 : (int)k == iy ? 1 : 2] = (s == "nan" || s == "NaN") ? NAN : strtod(s.c_str(), nullptr);
                 else if ((int)k == ic) {
@@ -473,6 +490,7 @@ extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_
                 t += F[k].count;
             }
             store(i, v, c);
+            if (normals) store_normal(i, w);
         }
     } else if (data == "binary" || data == "binary_compressed") {
         std::vector<uint8_t> soa;
@@ -498,11 +516,97 @@ extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_
         for (size_t i = 0; i < m; ++i) {
             const double v[3] = {field_value(at(i, ix), F[ix]), field_value(at(i, iy), F[iy]), field_value(at(i, iz), F[iz])};
             store(i, v, ic >= 0 ? color_bits(at(i, ic)) : 0u);
+            if (normals) {
+                float w[4];
+                for (int q = 0; q < 4; ++q) {
+                    if (F[in[q]].type == 'F' && F[in[q]].size == 4) memcpy(&w[q], at(i, in[q]), 4);   // the bits
+                    else w[q] = (float)field_value(at(i, in[q]), F[in[q]]);
+                }
+                store_normal(i, w);
+            }
         }
     } else {
         r360_set_error("%s: unknown DATA %s", path, data.c_str());
         return -1;
     }
+    return 0;
+}
+
+extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_t cap, size_t* n_out, int* width,
+                             int* height) {
+    return pcd_read_fields(path, xyz, rgba, nullptr, nullptr, false, cap, n_out, width, height);
+}
+
+extern "C" int r360_pcd_read_normals(const char* path, float* xyz, uint32_t* rgba, float* normals, float* curvature,
+                                     size_t cap, size_t* n) {
+    return pcd_read_fields(path, xyz, rgba, normals, curvature, true, cap, n, nullptr, nullptr);
+}
+
+// pcl::PointXYZRGBNormal: x y z rgba normal_x normal_y normal_z curvature, 32 bytes per point, unorganised.  The modes
+// and the codec are r360_pcd_write's; ascii prints the normals and the curvature with nine digits, which return the bits.
+extern "C" int r360_pcd_write_normals(const char* path, const float* xyz, const uint32_t* rgba, const float* normals,
+                                      const float* curvature, size_t n, int mode) {
+    // binary_compressed records the block's size in 32 bits
+    if (!path || (n && !xyz) || mode < 0 || mode > 2 || n > (size_t)1 << 30 || (mode == 2 && n >= (size_t)1 << 27)) {
+        r360_set_error("bad argument");
+        return -2;
+    }
+    std::ofstream o(path, std::ios::binary);
+    if (!o) { r360_set_error("cannot create %s", path); return -1; }
+    o << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgba normal_x normal_y normal_z curvature\n"
+         "SIZE 4 4 4 4 4 4 4 4\nTYPE F F F U F F F F\nCOUNT 1 1 1 1 1 1 1 1\nWIDTH " << n << "\nHEIGHT 1\n"
+         "VIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << n << "\n";
+    // one point's eight 4-byte fields
+    auto fields = [&](size_t i, uint32_t* w) {
+        memcpy(w, &xyz[3 * i], 12);
+        w[3] = rgba ? rgba[i] : 0u;
+        if (normals) memcpy(w + 4, &normals[3 * i], 12); else w[4] = w[5] = w[6] = 0u;
+        if (curvature) memcpy(w + 7, &curvature[i], 4); else w[7] = 0u;
+    };
+    if (mode == 0) {
+        o << "DATA ascii\n";
+        std::string line;
+        char buf[32];
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t w[8];
+            fields(i, w);
+            line.clear();
+            for (int k = 0; k < 8; ++k) {
+                if (k == 3) {
+                    snprintf(buf, sizeof buf, "%u", w[3]);
+                } else {
+                    float v;
+                    memcpy(&v, &w[k], 4);
+                    if (std::isnan(v)) snprintf(buf, sizeof buf, "nan");
+                    else snprintf(buf, sizeof buf, k < 3 ? "%.8g" : "%.9g", (double)v);
+                }
+                line += buf;
+                line += k == 7 ? '\n' : ' ';
+            }
+            o.write(line.data(), (std::streamsize)line.size());
+        }
+    } else {
+        std::vector<uint8_t> rec(32 * n);
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t w[8];
+            fields(i, w);
+            if (mode == 1) memcpy(&rec[32 * i], w, 32);
+            else for (int k = 0; k < 8; ++k) memcpy(&rec[4 * (k * n + i)], &w[k], 4);   // field-major
+        }
+        if (mode == 1) {
+            o << "DATA binary\n";
+            o.write((const char*)rec.data(), (std::streamsize)rec.size());
+        } else {
+            o << "DATA binary_compressed\n";
+            const std::vector<uint8_t> z = lzf_compress(rec.data(), rec.size());
+            const uint32_t zs = (uint32_t)z.size(), us = (uint32_t)rec.size();
+            o.write((const char*)&zs, 4);
+            o.write((const char*)&us, 4);
+            o.write((const char*)z.data(), (std::streamsize)z.size());
+        }
+    }
+    o.close();
+    if (!o) { r360_set_error("write failed: %s", path); return -1; }
     return 0;
 }
 

@@ -63,6 +63,41 @@ void make_grid(const float mn[3], const float mx[3], double limit, int ring, Out
     G->pad = 0;
 }
 
+}  // namespace
+
+int outlier_build_grid(r360_ctx* ctx, const uint4* pts, size_t n, const MapHdr& bounds, double limit, int ring,
+                       OutlierGrid* G, size_t* table_cap) {
+    OutlierState& S = ctx->outl;
+    hipStream_t st = ctx->stream;
+    const size_t nf = (size_t)bounds.count;
+    float mn[3], mx[3];
+    for (int k = 0; k < 3; ++k) { mn[k] = ord2f(bounds.mn[k]); mx[k] = ord2f(bounds.mx[k]); }
+    make_grid(mn, mx, limit, ring, G);
+    size_t cap = 1024;
+    while (cap < 2 * nf) cap <<= 1;   // a power of two (the probe mask), at most half full
+    *table_cap = cap;
+    const size_t nb_scan = (std::max(cap, n) + R360_OUTLIER_SCAN_BLOCK - 1) / R360_OUTLIER_SCAN_BLOCK;
+    if (grow(ctx, S.pslot, n) || grow(ctx, S.keys, cap) || grow(ctx, S.cnt, cap) || grow(ctx, S.start, cap) ||
+        grow(ctx, S.fill, cap) || grow(ctx, S.spts, nf) || grow(ctx, S.bsum, nb_scan))
+        return -1;
+    R360_HIP(hipMemsetAsync(S.keys.get(), 0, sizeof(unsigned long long) * cap, st));
+    R360_HIP(hipMemsetAsync(S.cnt.get(), 0, sizeof(unsigned) * cap, st));
+    R360_HIP(hipMemsetAsync(S.fill.get(), 0, sizeof(unsigned) * cap, st));
+    if (launch_out_cells(st, pts, n, *G, S.keys.get(), cap, S.cnt.get(), S.pslot.get(), S.d_hdr.get())) return -1;
+    if (launch_out_scan(st, S.cnt.get(), cap, S.bsum.get(), S.start.get(), nullptr)) return -1;
+    return launch_out_scatter(st, pts, n, S.pslot.get(), S.start.get(), S.fill.get(), S.spts.get(), nf, S.d_hdr.get());
+}
+
+int outlier_upload_cloud(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n) {
+    OutlierState& S = ctx->outl;
+    if (grow(ctx, S.in, n) || grow(ctx, S.out, n) || grow(ctx, S.up_xyz, 3 * n) || grow(ctx, S.up_rgba, n)) return -1;
+    R360_HIP(hipMemcpyAsync(S.up_xyz.get(), xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
+    if (rgba) R360_HIP(hipMemcpyAsync(S.up_rgba.get(), rgba, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
+    return launch_map_pack_host(ctx->stream, S.up_xyz.get(), rgba ? S.up_rgba.get() : nullptr, n, S.in.get());
+}
+
+namespace {
+
 // The filter named by prm on pts[0 .. n).  FILTER: the kept points into out (room for n), their number in *m.  HOOK:
 // S.score (statistical) or S.count (radius, the full counts) filled for every row, nothing compacted.  Synchronous.
 int outlier_run(r360_ctx* ctx, const uint4* pts, size_t n, const r360_outlier_params& prm, Mode mode, uint4* out,
@@ -90,24 +125,11 @@ int outlier_run(r360_ctx* ctx, const uint4* pts, size_t n, const r360_outlier_pa
     const size_t nf = (size_t)S.h_bounds.get()->count;
     z.n_finite = nf;
     if (nf > 0) {
-        float mn[3], mx[3];
-        for (int k = 0; k < 3; ++k) { mn[k] = ord2f(S.h_bounds.get()->mn[k]); mx[k] = ord2f(S.h_bounds.get()->mx[k]); }
         const double limit = stat ? (double)prm.max_dist : (double)prm.radius;
         OutlierGrid G;
+        size_t cap = 0;
         // the k-NN walk prunes cells by their distance, so finer cells save candidates; the count reads them all
-        make_grid(mn, mx, limit, stat ? 2 : 1, &G);
-        size_t cap = 1024;
-        while (cap < 2 * nf) cap <<= 1;   // a power of two (the probe mask), at most half full
-        const size_t nb_scan = (std::max(cap, n) + R360_OUTLIER_SCAN_BLOCK - 1) / R360_OUTLIER_SCAN_BLOCK;
-        if (grow(ctx, S.keys, cap) || grow(ctx, S.cnt, cap) || grow(ctx, S.start, cap) || grow(ctx, S.fill, cap) ||
-            grow(ctx, S.spts, nf) || grow(ctx, S.bsum, nb_scan))
-            return -1;
-        R360_HIP(hipMemsetAsync(S.keys.get(), 0, sizeof(unsigned long long) * cap, st));
-        R360_HIP(hipMemsetAsync(S.cnt.get(), 0, sizeof(unsigned) * cap, st));
-        R360_HIP(hipMemsetAsync(S.fill.get(), 0, sizeof(unsigned) * cap, st));
-        if (launch_out_cells(st, pts, n, G, S.keys.get(), cap, S.cnt.get(), S.pslot.get(), S.d_hdr.get())) return -1;
-        if (launch_out_scan(st, S.cnt.get(), cap, S.bsum.get(), S.start.get(), nullptr)) return -1;
-        if (launch_out_scatter(st, pts, n, S.pslot.get(), S.start.get(), S.fill.get(), S.spts.get(), nf, S.d_hdr.get())) return -1;
+        if (outlier_build_grid(ctx, pts, n, *S.h_bounds.get(), limit, stat ? 2 : 1, &G, &cap)) return -1;
         const double lim2 = limit * limit;
         if (stat) {
             if (launch_outlier_knn(st, S.spts.get(), nf, G, S.keys.get(), cap, S.start.get(), S.cnt.get(), lim2, prm.mean_k,
@@ -146,14 +168,6 @@ int outlier_run(r360_ctx* ctx, const uint4* pts, size_t n, const r360_outlier_pa
     return 0;
 }
 
-int upload_cloud(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n) {
-    OutlierState& S = ctx->outl;
-    if (grow(ctx, S.in, n) || grow(ctx, S.out, n) || grow(ctx, S.up_xyz, 3 * n) || grow(ctx, S.up_rgba, n)) return -1;
-    R360_HIP(hipMemcpyAsync(S.up_xyz.get(), xyz, sizeof(float) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
-    if (rgba) R360_HIP(hipMemcpyAsync(S.up_rgba.get(), rgba, sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream));
-    return launch_map_pack_host(ctx->stream, S.up_xyz.get(), rgba ? S.up_rgba.get() : nullptr, n, S.in.get());
-}
-
 }  // namespace
 
 extern "C" void r360_outlier_default_params(r360_outlier_params* p) {
@@ -178,7 +192,7 @@ extern "C" int r360_cloud_filter_outliers(r360_ctx* ctx, const float* xyz, const
     if (n == 0) return 0;
     if (bind_device(ctx->device)) return -1;
     OutlierState& S = ctx->outl;
-    if (upload_cloud(ctx, xyz, rgba, n)) return -1;
+    if (outlier_upload_cloud(ctx, xyz, rgba, n)) return -1;
     size_t m = 0;
     if (int rc = outlier_run(ctx, S.in.get(), n, *params, FILTER, S.out.get(), S.out.cap(), &m, stats)) return rc;
     *n_out = m;
@@ -205,6 +219,7 @@ extern "C" int r360_ctx_map_filter_outliers(r360_ctx* ctx, const r360_outlier_pa
         return rc;
     M.cur = other;
     M.map_n = m;
+    ctx->nrm.map_valid = false;
     return 0;
 }
 
@@ -216,7 +231,7 @@ extern "C" int r360_cloud_outlier_eval(r360_ctx* ctx, const float* xyz, size_t n
     if (n == 0) return 0;
     if (bind_device(ctx->device)) return -1;
     OutlierState& S = ctx->outl;
-    if (upload_cloud(ctx, xyz, nullptr, n)) return -1;
+    if (outlier_upload_cloud(ctx, xyz, nullptr, n)) return -1;
     size_t m = 0;
     if (int rc = outlier_run(ctx, S.in.get(), n, *params, HOOK, nullptr, 0, &m, nullptr)) return rc;
     if (params->kind == R360_OUTLIER_STATISTICAL) {

@@ -25,19 +25,7 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int WALK_TPB = 64;       // one wave per workgroup: the LDS columns are k x 64 doubles
-constexpr unsigned NOSLOT = 0xffffffffu;
-constexpr unsigned long long OCCUPIED = 1ull << 63;
-
-__device__ __forceinline__ bool finite_bits(unsigned u) { return (u & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ unsigned long long mix64(unsigned long long h) {   // murmur3's 64-bit finaliser
-    h ^= h >> 33; h *= 0xff51afd7ed558ccdull; h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull; h ^= h >> 33;
-    return h;
-}
-// a cell's coordinates (each in [0, 2^21)) as a non-zero key
-__device__ __forceinline__ unsigned long long cell_key(long long cx, long long cy, long long cz) {
-    return OCCUPIED | (unsigned long long)cz << 42 | (unsigned long long)cy << 21 | (unsigned long long)cx;
-}
-__device__ __forceinline__ bool cell_in_range(long long c) { return c >= 0 && c < (1ll << 21); }
+#include "sparse_grid.inc"   // cell keys, find_cell, axis_gap: shared with normal_kernels.hip
 
 __global__ void __launch_bounds__(TPB) k_out_init(size_t n, double* __restrict__ score, int* __restrict__ count,
                                                   unsigned* __restrict__ keep) {
@@ -150,25 +138,6 @@ __global__ void __launch_bounds__(TPB) k_out_scatter(const uint4* __restrict__ p
         if (pos >= nf) { atomicOr(&hdr->err, 2u); continue; }
         spts[pos] = make_float4(__uint_as_float(p.x), __uint_as_float(p.y), __uint_as_float(p.z), __uint_as_float((unsigned)i));
     }
-}
-
-// the occupied cell with this key: its slot, or NOSLOT
-__device__ __forceinline__ unsigned find_cell(const unsigned long long* __restrict__ keys, unsigned mask, unsigned long long key) {
-    unsigned h = (unsigned)mix64(key) & mask;
-    for (unsigned probe = 0; probe <= mask; ++probe) {
-        const unsigned long long k = keys[h];
-        if (k == key) return h;
-        if (k == 0ull) return NOSLOT;
-        h = (h + 1) & mask;
-    }
-    return NOSLOT;
-}
-
-// lower bound, in cell edges, of the distance along one axis from a point at fraction u of its cell to the cell o
-// cells away; the 1e-6 of slack is far above what the rounding of x / ec can move a point across a cell face
-__device__ __forceinline__ double axis_gap(int o, double u) {
-    const double g = o < 0 ? u + (double)(-o - 1) : (o > 0 ? (double)(o - 1) + (1.0 - u) : 0.0);
-    return fmax(g - 1.0e-6, 0.0);
 }
 
 // The walk of point t (in cell order) over the cells around its own, its own first.  KNN: the k smallest squared

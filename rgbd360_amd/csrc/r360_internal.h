@@ -390,6 +390,35 @@ int launch_out_flag_stat(hipStream_t st, const double* score, size_t n, const Ou
 int launch_out_flag_radius(hipStream_t st, const int* count, size_t n, int min_neighbors, unsigned* keep);
 int launch_out_compact(hipStream_t st, const uint4* pts, size_t n, const unsigned* keep, const unsigned* pos, uint4* out,
                        size_t out_cap, OutlierHdr* hdr);
+// host/outliers.cpp, shared with host/normals.cpp.  outlier_upload_cloud: a host cloud packed into ctx->outl.in (enqueued).
+// outlier_build_grid: the sparse grid over the finite points of pts[0 .. n), whose bounds and count `bounds` holds, for a
+// search bound `limit` read as `ring` cells: G and the table's capacity, with keys / cnt / start / spts of ctx->outl
+// filled (enqueued; error bits go to ctx->outl.d_hdr, which the caller has zeroed).
+int outlier_upload_cloud(r360_ctx* ctx, const float* xyz, const uint32_t* rgba, size_t n);
+int outlier_build_grid(r360_ctx* ctx, const uint4* pts, size_t n, const MapHdr& bounds, double limit, int ring,
+                       OutlierGrid* G, size_t* table_cap);
+
+// ------------------------------------------------------------------ surface normals (kernels/normal_kernels.hip, host/normals.cpp)
+constexpr int R360_NORMAL_KMAX = 64;               // k the kernel's LDS columns hold: 64 lanes x 64 x 12 B = 48 KiB
+constexpr int R360_NORMAL_VIEWMAX = 4096;
+struct NormalHdr { unsigned long long n_short, sum_neighbors; };
+// the parity hook's outputs, all NULL in the product calls
+struct NormalEval { int* knn; int* count; double* normal; double* eig; double* curvature; };
+// What the normal estimation holds on the device, grown on demand and freed with the context; the grid is ctx->outl's.
+struct NormalState {
+    DevBuf<NormalHdr> d_hdr; PinnedBuf<NormalHdr> h_hdr;
+    DevBuf<float> view;                  // [n_view][3]
+    DevBuf<float4> out;                  // [n] {nx, ny, nz, curvature} of the running call, at the input index
+    DevBuf<float4> map;                  // [map_n] the map's normals in the map's order, while map_valid
+    size_t map_n = 0;
+    bool map_valid = false;              // cleared by whatever changes the map
+    DevBuf<int> knn, count;              // the parity hook: [n][k], [n]
+    DevBuf<double> ev;                   // the parity hook: [n][7] normal, eigenvalues ascending, curvature
+};
+int launch_normals_init(hipStream_t st, size_t n, int k, float4* out, const NormalEval& ev);
+int launch_normals(hipStream_t st, const uint4* pts, const float4* spts, size_t nf, const OutlierGrid& G,
+                   const unsigned long long* keys, size_t table_cap, const unsigned* start, const unsigned* cnt, double lim2,
+                   int k, const float* view, int n_view, float4* out, NormalHdr* hdr, const NormalEval& ev);
 
 // ------------------------------------------------------------------ Generalized-ICP (kernels/gicp_kernels.hip, host/gicp.cpp)
 // GicpGrid, the uniform grid over a cloud's bounding box, and the host-only logic: host/gicp_host.h
@@ -555,6 +584,7 @@ struct r360_ctx {
     MapState vmap;                         // voxel-filter scratch and the context's global map (host/map.cpp)
     GicpState gicp;                        // Generalized-ICP clouds, indices and pass buffers (host/gicp.cpp)
     OutlierState outl;                     // outlier filters: sparse grid, scores, compaction (host/outliers.cpp)
+    NormalState nrm;                       // surface normals: a call's output, the map's normals (host/normals.cpp)
     TopoState topo;                        // spectral partitioning: matrices, cluster lists, scratch (host/topo.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
