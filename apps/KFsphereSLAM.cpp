@@ -34,9 +34,17 @@
 // pcl::NormalEstimation over at most K points within R m, turned towards the nearest optimised keyframe position), after
 // --clean-map if given, and prints one more line, "map normals: <points> points, <short> short, <mean> neighbours on
 // average".  --save-map file.pcd writes the final map (binary), with its normals when they were estimated.
+// --clean-map cluster:TOL,MIN is the third kind: r360::GlobalMap360::removeSmallClusters keeps the connected components of
+// "closer than TOL m" with at least MIN points (pcl::EuclideanClusterExtraction), and the line reads "map cleaned:
+// <before> -> <after> points (<components> components, <kept> kept)".  --map-clusters TOL,MIN[,ANGLE_DEG] clusters the
+// final map where it lies (r360::GlobalMap360::cluster), after --clean-map; with an angle it is the normal-aware form on
+// the normals of --map-normals, which it then requires and follows.  It prints one more line, "map clusters: <points>
+// points, <components> components, <clusters> kept, largest <size>".  --save-clusters file.pcd writes the labelled map
+// (binary, x y z rgba label).
 //   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]
 //                       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]
-//                       [--map-normals K,R] [--save-map file.pcd]
+//                       [--map-normals K,R] [--save-map file.pcd] [--map-clusters TOL,MIN[,ANGLE_DEG]] [--save-clusters file.pcd]
+//                       (--clean-map also takes cluster:TOL,MIN)
 //          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
 //          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
 #include <rgbd360/rgbd360.h>
@@ -85,6 +93,13 @@ int main(int argc, char** argv) {
     r360_normal_params normal_prm;
     r360_normal_default_params(&normal_prm);
     std::string save_map;                                // --save-map
+    bool clean_clusters = false;                         // --clean-map cluster:TOL,MIN
+    r360_cluster_params clean_clu;
+    r360_cluster_default_params(&clean_clu);
+    bool map_clusters = false, cluster_normals = false;  // --map-clusters, with an angle
+    r360_cluster_params cluster_prm;
+    r360_cluster_default_params(&cluster_prm);
+    std::string save_clusters;                           // --save-clusters
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
         if (a == "--clean-map" && k + 1 < argc) {
@@ -97,6 +112,9 @@ int main(int argc, char** argv) {
             } else if (v.compare(0, 7, "radius:") == 0) {
                 clean.kind = R360_OUTLIER_RADIUS;
                 bad_arg = bad_arg || std::sscanf(v.c_str() + 7, "%f,%d", &clean.radius, &clean.min_neighbors) != 2;
+            } else if (v.compare(0, 8, "cluster:") == 0) {
+                clean_clusters = true;
+                bad_arg = bad_arg || std::sscanf(v.c_str() + 8, "%f,%d", &clean_clu.tolerance, &clean_clu.min_size) != 2;
             } else {
                 bad_arg = true;
             }
@@ -124,6 +142,17 @@ int main(int argc, char** argv) {
             map_normals = true;
             bad_arg = bad_arg || std::sscanf(argv[++k], "%d,%f", &normal_prm.k, &normal_prm.radius) != 2;
         }
+        else if (a == "--save-clusters" && k + 1 < argc) save_clusters = argv[++k];
+        else if (a == "--map-clusters" && k + 1 < argc) {
+            map_clusters = true;
+            float deg = 0.f;
+            const int got = std::sscanf(argv[++k], "%f,%d,%f", &cluster_prm.tolerance, &cluster_prm.min_size, &deg);
+            bad_arg = bad_arg || got < 2;
+            if (got == 3) {
+                cluster_normals = true;
+                cluster_prm.eps_angle = deg * 3.14159265359f / 180.f;
+            }
+        }
         else if (a == "--submaps") submaps = true;
         else if (a == "--synthetic-frames" && k + 1 < argc) { frames_arg = argv[++k]; synthetic = true; }
         else if (a == "--synthetic" && k + 1 < argc) { n_synth = std::atoi(argv[++k]); synthetic = true; }
@@ -137,11 +166,12 @@ int main(int argc, char** argv) {
         p = q + 1;
     }
     for (int k = 0; k < n_synth && frames_arg.empty(); ++k) order.push_back(k);
+    bad_arg = bad_arg || (cluster_normals && !map_normals) || (!save_clusters.empty() && !map_clusters);
     if (bad_arg || (synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
         std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
                              "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n"
                              "       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]\n"
-                             "       [--map-normals K,R] [--save-map file.pcd]\n"
+                             "       [--map-normals K,R] [--save-map file.pcd] [--map-clusters TOL,MIN[,ANGLE_DEG]] [--save-clusters file.pcd]\n"
                              "  --robust       loop edges get the kernel, of width D on sqrt(chi2); chain and PbMap edges stay quadratic\n"
                              "  --reject-chi2  after each optimisation loop edges with chi2 > T are deactivated and the graph is optimised again\n"
                              "  --false-loop   when keyframe J is added, also add a wrong loop edge I -> J (demonstration)\n"
@@ -152,7 +182,11 @@ int main(int argc, char** argv) {
                              "                 or the radius (radius:R in m,min neighbours) outlier filter, on the GPU\n"
                              "  --map-normals  normals and curvature of the final map from at most K points within R m, turned towards the\n"
                              "                 nearest keyframe position, on the GPU (after --clean-map)\n"
-                             "  --save-map     the final map as a binary PCD file, with the normals when they were estimated\n", argv[0]);
+                             "  --save-map     the final map as a binary PCD file, with the normals when they were estimated\n"
+                             "  --clean-map cluster:TOL,MIN  keeps the connected components of 'closer than TOL m' with at least MIN points\n"
+                             "  --map-clusters the final map's Euclidean clusters (tolerance in m, least size), after --clean-map; with an angle\n"
+                             "                 in degrees two neighbours' normals must also agree within it (needs --map-normals)\n"
+                             "  --save-clusters  the clustered map as a binary PCD file with a label field (needs --map-clusters)\n", argv[0]);
         return 1;
     }
     const bool edge_report = robust_kind != R360_GRAPH_KERNEL_NONE || reject_chi2 >= 0.0 || false_from >= 0;
@@ -420,7 +454,12 @@ int main(int argc, char** argv) {
             sizes[which] = map.size();
         }
         std::printf("global map: %zu points at the chained poses, %zu at the optimised poses\n", sizes[0], sizes[1]);
-        if (clean_map) {   // the map holds the fusion at the optimised poses
+        if (clean_map && clean_clusters) {
+            r360_cluster_stats st;
+            map.removeSmallClusters(clean_clu, false, &st);
+            std::printf("map cleaned: %zu -> %zu points (%zu components, %zu kept)\n", sizes[1], map.size(), st.n_components,
+                        st.n_clusters);
+        } else if (clean_map) {   // the map holds the fusion at the optimised poses
             r360_outlier_stats st;
             map.removeOutliers(clean, &st);
             std::printf("map cleaned: %zu -> %zu points (%zu short)\n", sizes[1], map.size(), st.n_short);
@@ -433,6 +472,15 @@ int main(int argc, char** argv) {
             map.estimateNormals(normal_prm, views, &st);
             std::printf("map normals: %zu points, %zu short, %.3f neighbours on average\n", st.n_in, st.n_short,
                         st.n_finite ? double(st.sum_neighbors) / double(st.n_finite) : 0.0);
+        }
+        if (map_clusters) {
+            r360_cluster_stats st;
+            map.cluster(cluster_prm, cluster_normals, &st);
+            std::vector<r360_cluster_info> clusters;
+            map.getClusters(clusters);
+            std::printf("map clusters: %zu points, %zu components, %zu kept, largest %d\n", st.n_in, st.n_components,
+                        st.n_clusters, clusters.empty() ? 0 : clusters[0].size);
+            if (!save_clusters.empty()) map.savePCDLabels(save_clusters, 1);
         }
         if (!save_map.empty()) {
             if (map_normals) {

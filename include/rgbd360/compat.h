@@ -33,6 +33,7 @@
 using r360::Calib360;
 using r360::Calibration;
 using r360::ControlPlanes;
+using r360::EuclideanClusterExtraction;
 using r360::FilterPointCloud;
 using r360::GeneralizedIterativeClosestPoint;
 using r360::Frame360;
@@ -40,6 +41,7 @@ using r360::GraphOptimizer;
 using r360::NormalEstimation;
 using r360::PbMap;
 using r360::Plane;
+using r360::PointIndices;
 using r360::RegisterPhotoICP;
 using r360::RegisterRGBD360;
 // Map360.h / TopologicalMap360.h / Relocalizer360.h: opt-in, since call-site files written before these classes

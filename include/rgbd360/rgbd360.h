@@ -234,6 +234,11 @@ struct PointCloudNormal {
     }
 };
 
+// One cluster's member rows of the input cloud, ascending (pcl::PointIndices).
+struct PointIndices {
+    std::vector<int> indices;
+};
+
 class Context {
   public:
     explicit Context(int device = 0) { check(r360_ctx_create(device, &h_), "r360_ctx_create"); }
@@ -915,6 +920,41 @@ class GlobalMap360 {
                                      nrm.curvature.data(), cloud.size(), mode),
               "GlobalMap360::savePCDNormals");
     }
+    // Euclidean clusters of the map where it lies (r360_ctx_map_cluster): labels and records stay on the GPU, valid
+    // until the map next changes.  use_normals: the normal-aware form on the map's normals (estimateNormals first)
+    void cluster(const r360_cluster_params& params, bool use_normals = false, r360_cluster_stats* stats = nullptr) {
+        check(r360_ctx_map_cluster(ctx_->get(), &params, use_normals ? 1 : 0, stats), "GlobalMap360::cluster");
+    }
+    // the map's labels in the order of download() (-1: in no cluster); throws when the map changed since cluster()
+    void getLabels(std::vector<int>& labels) const {
+        size_t n = 0;
+        check(r360_ctx_map_download_labels(ctx_->get(), nullptr, 0, &n), "GlobalMap360::getLabels");
+        labels.resize(n);
+        check(r360_ctx_map_download_labels(ctx_->get(), labels.data(), n, &n), "GlobalMap360::getLabels");
+    }
+    // the clusters' records, largest first
+    void getClusters(std::vector<r360_cluster_info>& info) const {
+        size_t n = 0;
+        check(r360_ctx_map_cluster_info(ctx_->get(), nullptr, 0, &n), "GlobalMap360::getClusters");
+        info.resize(n);
+        check(r360_ctx_map_cluster_info(ctx_->get(), info.data(), n, &n), "GlobalMap360::getClusters");
+    }
+    // keeps exactly the points of the clusters within the size bounds (r360_ctx_map_filter_clusters), in HBM; the map's
+    // normals and labels become invalid, as after removeOutliers
+    void removeSmallClusters(const r360_cluster_params& params, bool use_normals = false,
+                             r360_cluster_stats* stats = nullptr) {
+        check(r360_ctx_map_filter_clusters(ctx_->get(), &params, use_normals ? 1 : 0, stats),
+              "GlobalMap360::removeSmallClusters");
+    }
+    // the map with its labels as a PointXYZRGBL file (r360_pcd_write_labels; mode as r360_pcd_write)
+    void savePCDLabels(const std::string& path, int mode = 0) const {
+        PointCloud cloud;
+        std::vector<int> labels;
+        download(cloud);
+        getLabels(labels);
+        check(r360_pcd_write_labels(path.c_str(), cloud.xyz.data(), cloud.rgba.data(), labels.data(), cloud.size(), mode),
+              "GlobalMap360::savePCDLabels");
+    }
   private:
     std::shared_ptr<Context> keep_;
     Context* ctx_;
@@ -963,6 +1003,55 @@ class NormalEstimation {
     float radius_ = 0.f, bound_ = 0.5f;
     std::vector<float> views_ = {0.f, 0.f, 0.f};
     r360_normal_stats stats_ = {0, 0, 0, 0};
+};
+
+// pcl::EuclideanClusterExtraction with PCL's names, on the GPU of the calling thread's default context or of the Context
+// given (r360_cloud_clusters).  extract() returns the clusters largest first (ties by their smallest
+// row), each with its rows ascending.  Extension: setInputNormals / setEpsAngle select the normal-aware form, which in
+// PCL is the free function pcl::extractEuclideanClusters(cloud, normals, tolerance, tree, clusters, eps_angle, ...).
+// The input cloud and normals are referenced, not copied: they must outlive extract().
+class EuclideanClusterExtraction {
+  public:
+    EuclideanClusterExtraction() { r360_cluster_default_params(&prm_); }
+    explicit EuclideanClusterExtraction(Context& ctx) : ctx_(&ctx) { r360_cluster_default_params(&prm_); }
+    void setClusterTolerance(double tolerance) { prm_.tolerance = float(tolerance); }
+    double getClusterTolerance() const { return prm_.tolerance; }
+    void setMinClusterSize(int n) { prm_.min_size = n; }
+    int getMinClusterSize() const { return prm_.min_size; }
+    void setMaxClusterSize(int n) { prm_.max_size = n; }
+    int getMaxClusterSize() const { return prm_.max_size; }
+    void setInputCloud(const PointCloud& cloud) { cloud_ = &cloud; }
+    void setInputNormals(const PointCloudNormal& normals) { normals_ = &normals; }   // extension
+    void setEpsAngle(double radians) { prm_.eps_angle = float(radians); }            // extension
+    const r360_cluster_stats& stats() const { return stats_; }
+    const std::vector<int>& getLabels() const { return labels_; }
+    const std::vector<r360_cluster_info>& getClusterInfo() const { return info_; }
+    void extract(std::vector<PointIndices>& clusters) {
+        if (!cloud_) throw std::invalid_argument("EuclideanClusterExtraction::extract: no input cloud");
+        if (normals_ && normals_->size() != cloud_->size())
+            throw std::invalid_argument("EuclideanClusterExtraction::extract: normals and cloud differ in size");
+        Context& c = ctx_ ? *ctx_ : default_context();
+        const size_t n = cloud_->size();
+        labels_.assign(n, -1);
+        info_.resize(n / size_t(prm_.min_size > 0 ? prm_.min_size : 1) + 1);   // no more clusters than that
+        size_t nk = 0;
+        check(r360_cloud_clusters(c.get(), cloud_->xyz.data(), normals_ ? normals_->normals.data() : nullptr, n, &prm_,
+                                  labels_.data(), info_.data(), info_.size(), &nk, &stats_),
+              "EuclideanClusterExtraction::extract");
+        info_.resize(nk);
+        clusters.assign(nk, PointIndices());
+        for (size_t k = 0; k < nk; ++k) clusters[k].indices.reserve(size_t(info_[k].size));
+        for (size_t i = 0; i < n; ++i)
+            if (labels_[i] >= 0) clusters[size_t(labels_[i])].indices.push_back(int(i));
+    }
+  private:
+    Context* ctx_ = nullptr;
+    const PointCloud* cloud_ = nullptr;
+    const PointCloudNormal* normals_ = nullptr;
+    r360_cluster_params prm_;
+    r360_cluster_stats stats_ = {0, 0, 0, 0, 0};
+    std::vector<int> labels_;
+    std::vector<r360_cluster_info> info_;
 };
 
 // ------------------------------------------------------------------ Generalized-ICP

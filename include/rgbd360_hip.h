@@ -825,6 +825,56 @@ int r360_pcd_write_normals(const char* path, const float* xyz, const uint32_t* r
 int r360_pcd_read_normals(const char* path, float* xyz, uint32_t* rgba, float* normals, float* curvature, size_t cap,
                           size_t* n);
 
+/* ---------------------------------------------------------------- Euclidean cluster extraction
+ * pcl::EuclideanClusterExtraction and the normal-aware pcl::extractEuclideanClusters overload, restated from PCL 1.7
+ * segmentation/extract_clusters.h (unpinned), for a host cloud and for the context's global map where it lies.  The
+ * statement is tests/cluster_model.py and DESIGN.md §5b-4.
+ * A row with a non-finite coordinate is dropped: label -1, member of nothing.  Two finite rows i != j are joined iff
+ * dx*dx + dy*dy + dz*dz <= (double)tolerance^2 (closed; double of the float coordinates, left to right) and, when
+ * normals ([n][3]) are given, (nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j >= cos((double)eps_angle) in double of the floats:
+ * the normals are taken as given, neither normalised nor sign-agnostic, and a row whose normal has a non-finite
+ * component is joined to nothing.  A component of that graph is a cluster iff min_size <= size <= max_size.  Clusters
+ * are ordered by size descending, ties by their smallest input index (root) ascending; label[i] is the cluster's rank,
+ * -1 for a dropped row and for a row of a rejected component.  Two calls give the same bytes.
+ * r360_cluster_info: size, root, min / max of the members' coordinates, their centroid, and of their covariance
+ * (fp64, two passes, / size) the eigenvalues ascending, the unit eigenvector of eig[0] with its largest-magnitude
+ * component positive (ties to the lower axis) and curvature = |eig[0]| / trace (0 when the trace is 0); eig, normal and
+ * curvature are NaN for fewer than 3 members.
+ * r360_cloud_clusters: normals NULL selects the plain form.  labels [n], info [info_cap], n_clusters and stats may be
+ * NULL; info_cap < the number of clusters is an error (< 0) that still sets *n_clusters (and labels and stats).
+ * r360_cloud_clusters_eval (parity hook): root [n] the smallest input index of the row's component (-1 dropped),
+ * comp_size [n] the component's size before the size bounds (-1 dropped).
+ * r360_ctx_map_cluster: labels and records of the context's map, kept on the device in the map's order until the map
+ * next changes (r360_ctx_map_reset, _add_cloud, _add_frame, _filter_outliers, _filter_clusters).  use_normals without
+ * valid map normals is an error (< 0); an empty map gives 0 and zero stats; an error leaves the map, its normals and its
+ * labels as they were.
+ * r360_ctx_map_download_labels / r360_ctx_map_cluster_info: an error (< 0) when the map has no valid labels; *n is the
+ * map's size / the number of clusters either way; cap < *n is an error (< 0); a NULL array: only *n.
+ * r360_ctx_map_filter_clusters: clusters, then keeps exactly the map points with label >= 0, compacted in HBM: the map
+ * stays in ascending voxel order and kept points keep their bits.  The map's normals and labels become invalid.
+ * r360_pcd_write_labels / _read_labels: a PointXYZRGBL cloud, FIELDS x y z rgba label (label U 4, -1 written as
+ * 4294967295), WIDTH n HEIGHT 1, in r360_pcd_write's modes.  rgba and labels may be NULL (written as 0 / read and
+ * dropped); read fails on a file without a label field; cap < *n reads the first cap points.
+ * Arguments: tolerance positive and finite, 1 <= min_size <= max_size, eps_angle in [0, pi] when normals are used,
+ * n <= 2^30 (R360_EINVAL otherwise, before any GPU work). */
+typedef struct { float tolerance; int min_size; int max_size; float eps_angle; } r360_cluster_params;
+typedef struct { size_t n_in, n_finite, n_components, n_clusters, n_clustered; } r360_cluster_stats;
+typedef struct { int size, root; float min[3], max[3]; double centroid[3], eig[3], normal[3], curvature; } r360_cluster_info;
+void r360_cluster_default_params(r360_cluster_params* params);
+int r360_cloud_clusters(r360_ctx* ctx, const float* xyz, const float* normals, size_t n, const r360_cluster_params* params,
+                        int* labels, r360_cluster_info* info, size_t info_cap, size_t* n_clusters,
+                        r360_cluster_stats* stats);
+int r360_cloud_clusters_eval(r360_ctx* ctx, const float* xyz, const float* normals, size_t n,
+                             const r360_cluster_params* params, int* labels, r360_cluster_info* info, size_t info_cap,
+                             size_t* n_clusters, r360_cluster_stats* stats, int* root, int* comp_size);
+int r360_ctx_map_cluster(r360_ctx* ctx, const r360_cluster_params* params, int use_normals, r360_cluster_stats* stats);
+int r360_ctx_map_download_labels(r360_ctx* ctx, int* labels, size_t cap, size_t* n);
+int r360_ctx_map_cluster_info(r360_ctx* ctx, r360_cluster_info* info, size_t cap, size_t* n);
+int r360_ctx_map_filter_clusters(r360_ctx* ctx, const r360_cluster_params* params, int use_normals,
+                                 r360_cluster_stats* stats);
+int r360_pcd_write_labels(const char* path, const float* xyz, const uint32_t* rgba, const int* labels, size_t n, int mode);
+int r360_pcd_read_labels(const char* path, float* xyz, uint32_t* rgba, int* labels, size_t cap, size_t* n);
+
 /* ---------------------------------------------------------------- Generalized-ICP
  * pcl::GeneralizedIterativeClosestPoint as Registration/RegisterPairRGBD360.cpp:109-149 calls it, restated (PCL is
  * not pinned): the statement is tests/gicp_model.py and DESIGN.md §5c.  Per cloud: rows with a non-finite coordinate

@@ -144,6 +144,46 @@ class NormalStats(C.Structure):
                 ("sum_neighbors", C.c_ulonglong)]
 
 
+class ClusterParams(C.Structure):
+    """r360_cluster_params — pcl::EuclideanClusterExtraction's tolerance and size bounds, and the angle of the
+    normal-aware form in radians (see include/rgbd360_hip.h)."""
+    _fields_ = [("tolerance", C.c_float), ("min_size", C.c_int), ("max_size", C.c_int), ("eps_angle", C.c_float)]
+
+    @classmethod
+    def default(cls) -> "ClusterParams":
+        p = cls()
+        lib().r360_cluster_default_params(C.byref(p))
+        return p
+
+    @classmethod
+    def make(cls, tolerance: float = 0.10, min_size: int = 100, max_size: int = 1 << 30,
+             eps_angle: "float | None" = None) -> "ClusterParams":
+        p = cls.default()
+        p.tolerance, p.min_size, p.max_size = tolerance, min_size, max_size
+        if eps_angle is not None:
+            p.eps_angle = eps_angle
+        return p
+
+
+class ClusterStats(C.Structure):
+    """r360_cluster_stats — what one cluster extraction saw."""
+    _fields_ = [("n_in", C.c_size_t), ("n_finite", C.c_size_t), ("n_components", C.c_size_t), ("n_clusters", C.c_size_t),
+                ("n_clustered", C.c_size_t)]
+
+
+class ClusterInfo(C.Structure):
+    """r360_cluster_info — one cluster's record."""
+    _fields_ = [("size", C.c_int), ("root", C.c_int), ("min", C.c_float * 3), ("max", C.c_float * 3),
+                ("centroid", C.c_double * 3), ("eig", C.c_double * 3), ("normal", C.c_double * 3), ("curvature", C.c_double)]
+
+
+# the records as a numpy structured array, field for field
+CLUSTER_INFO_DTYPE = np.dtype([("size", np.int32), ("root", np.int32), ("min", np.float32, 3), ("max", np.float32, 3),
+                               ("centroid", np.float64, 3), ("eig", np.float64, 3), ("normal", np.float64, 3),
+                               ("curvature", np.float64)])
+assert CLUSTER_INFO_DTYPE.itemsize == C.sizeof(ClusterInfo)
+
+
 class GraphParams(C.Structure):
     """r360_graph_params — pose-graph optimisation settings (see include/rgbd360_hip.h)."""
     _fields_ = [
@@ -504,6 +544,17 @@ _SIGS = [
                                           _DP]),
     ("r360_pcd_write_normals", C.c_int, [C.c_char_p, _FP, _P, _FP, _FP, C.c_size_t, C.c_int]),
     ("r360_pcd_read_normals", C.c_int, [C.c_char_p, _FP, _P, _FP, _FP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_cluster_default_params", None, [C.POINTER(ClusterParams)]),
+    ("r360_cloud_clusters", C.c_int, [_P, _FP, _FP, C.c_size_t, C.POINTER(ClusterParams), _IP, _P, C.c_size_t,
+                                      C.POINTER(C.c_size_t), C.POINTER(ClusterStats)]),
+    ("r360_cloud_clusters_eval", C.c_int, [_P, _FP, _FP, C.c_size_t, C.POINTER(ClusterParams), _IP, _P, C.c_size_t,
+                                           C.POINTER(C.c_size_t), C.POINTER(ClusterStats), _IP, _IP]),
+    ("r360_ctx_map_cluster", C.c_int, [_P, C.POINTER(ClusterParams), C.c_int, C.POINTER(ClusterStats)]),
+    ("r360_ctx_map_download_labels", C.c_int, [_P, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_ctx_map_cluster_info", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_ctx_map_filter_clusters", C.c_int, [_P, C.POINTER(ClusterParams), C.c_int, C.POINTER(ClusterStats)]),
+    ("r360_pcd_write_labels", C.c_int, [C.c_char_p, _FP, _P, _IP, C.c_size_t, C.c_int]),
+    ("r360_pcd_read_labels", C.c_int, [C.c_char_p, _FP, _P, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r360_gicp_default_params", None, [C.POINTER(GicpParams)]),
     ("r360_gicp_set_source", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
     ("r360_gicp_set_target", C.c_int, [_P, _FP, C.c_size_t, C.POINTER(GicpParams)]),
@@ -646,6 +697,27 @@ def pcd_read_normals(path: str):
     _check(lib().r360_pcd_read_normals(path.encode(), _fptr(xyz), _vptr(rgba), _fptr(nrm), _fptr(curv), n.value, C.byref(n)),
            "pcd_read_normals")
     return xyz, rgba, nrm, curv
+
+
+def write_pcd_labels(path: str, xyz, rgba, labels, mode: int = PCD_ASCII):
+    """A PointXYZRGBL cloud (x y z rgba label; -1 is written as 4294967295), unorganised, in pcd_write's modes."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    n = xyz.shape[0]
+    rgba = None if rgba is None else np.ascontiguousarray(rgba, np.uint32).reshape(-1)
+    labels = np.ascontiguousarray(labels, np.int32).reshape(-1)
+    assert labels.shape[0] == n and (rgba is None or rgba.shape[0] == n)
+    _check(lib().r360_pcd_write_labels(path.encode(), _fptr(xyz), None if rgba is None else _vptr(rgba),
+                                       labels.ctypes.data_as(_IP), n, mode), "write_pcd_labels")
+
+
+def read_pcd_labels(path: str):
+    """(xyz [n,3] f32, rgba [n] u32, labels [n] i32) of a PCD file that holds a label field."""
+    n = C.c_size_t()
+    _check(lib().r360_pcd_read_labels(path.encode(), None, None, None, 0, C.byref(n)), "read_pcd_labels")
+    xyz, rgba, labels = np.zeros((n.value, 3), np.float32), np.zeros(n.value, np.uint32), np.zeros(n.value, np.int32)
+    _check(lib().r360_pcd_read_labels(path.encode(), _fptr(xyz), _vptr(rgba), labels.ctypes.data_as(_IP), n.value,
+                                      C.byref(n)), "read_pcd_labels")
+    return xyz, rgba, labels
 
 
 def _fptr(a: np.ndarray):
@@ -865,6 +937,67 @@ class Context:
                                              knn.ctypes.data_as(_IP), count.ctypes.data_as(_IP), _dptr(nrm), _dptr(eig),
                                              _dptr(curv)), "normals_eval")
         return knn, count, nrm, eig, curv
+
+    def _clusters(self, xyz, prm, normals, hook):
+        xyz, _ = _cloud_arrays(xyz, None)
+        p = prm if prm is not None else ClusterParams.default()
+        n = xyz.shape[0]
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert nrm is None or nrm.shape[0] == n
+        labels, st, nk = np.full(n, -1, np.int32), ClusterStats(), C.c_size_t()
+        root, comp = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        cap = n // max(int(p.min_size), 1) + 1     # no more clusters than that
+        info = np.zeros(cap, CLUSTER_INFO_DTYPE)
+        args = [self.h, _fptr(xyz), None if nrm is None else _fptr(nrm), n, C.byref(p), labels.ctypes.data_as(_IP),
+                _vptr(info), cap, C.byref(nk), C.byref(st)]
+        if hook:
+            _check(lib().r360_cloud_clusters_eval(*args, root.ctypes.data_as(_IP), comp.ctypes.data_as(_IP)), "clusters_eval")
+            return labels, info[:nk.value].copy(), st, root, comp
+        _check(lib().r360_cloud_clusters(*args), "clusters")
+        return labels, info[:nk.value].copy(), st
+
+    def clusters(self, xyz, prm: "ClusterParams | None" = None, normals=None):
+        """pcl::EuclideanClusterExtraction on this context's GPU (r360_cloud_clusters): the connected components of
+        "closer than the tolerance" within the size bounds, largest first; with `normals` [n,3] the normal-aware form
+        (an edge also needs an angle of at most eps_angle between the two normals).  Returns (labels [n] i32, -1 = in no
+        cluster; info, a CLUSTER_INFO_DTYPE array with one record per cluster; ClusterStats)."""
+        return self._clusters(xyz, prm, normals, False)
+
+    def clusters_eval(self, xyz, prm: "ClusterParams | None" = None, normals=None):
+        """Parity hook (r360_cloud_clusters_eval): clusters()'s three, then root [n] i32 (the smallest index of the row's
+        component, -1 dropped) and comp_size [n] i32 (its size before the size bounds)."""
+        return self._clusters(xyz, prm, normals, True)
+
+    def map_cluster(self, prm: "ClusterParams | None" = None, use_normals: bool = False) -> "ClusterStats":
+        """The same on the context's global map where it lies; labels and records stay in HBM, valid until the map
+        changes.  use_normals: the normal-aware form on the map's normals (map_estimate_normals first)."""
+        p = prm if prm is not None else ClusterParams.default()
+        st = ClusterStats()
+        _check(lib().r360_ctx_map_cluster(self.h, C.byref(p), int(use_normals), C.byref(st)), "map_cluster")
+        return st
+
+    def map_labels(self) -> np.ndarray:
+        """The map's labels [n] i32 in the map's order; raises when the map changed since map_cluster."""
+        n = C.c_size_t()
+        _check(lib().r360_ctx_map_download_labels(self.h, None, 0, C.byref(n)), "map_labels")
+        labels = np.full(n.value, -1, np.int32)
+        _check(lib().r360_ctx_map_download_labels(self.h, labels.ctypes.data_as(_IP), n.value, C.byref(n)), "map_labels")
+        return labels
+
+    def map_clusters(self) -> np.ndarray:
+        """The map's cluster records (CLUSTER_INFO_DTYPE); raises when the map changed since map_cluster."""
+        n = C.c_size_t()
+        _check(lib().r360_ctx_map_cluster_info(self.h, None, 0, C.byref(n)), "map_clusters")
+        info = np.zeros(n.value, CLUSTER_INFO_DTYPE)
+        _check(lib().r360_ctx_map_cluster_info(self.h, _vptr(info), n.value, C.byref(n)), "map_clusters")
+        return info
+
+    def map_filter_clusters(self, prm: "ClusterParams | None" = None, use_normals: bool = False) -> "ClusterStats":
+        """Clusters the map and keeps exactly the points of the kept clusters, where the map lies in HBM."""
+        p = prm if prm is not None else ClusterParams.default()
+        st = ClusterStats()
+        _check(lib().r360_ctx_map_filter_clusters(self.h, C.byref(p), int(use_normals), C.byref(st)), "map_filter_clusters")
+        return st
 
     def _gicp_set(self, fn, xyz, params, what):
         xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)

@@ -385,9 +385,10 @@ extern "C" int r360_pcd_write(const char* path, const float* xyz, const uint32_t
 
 // Reads a .pcd into xyz [cap][3] / rgba [cap] (either may be NULL; a cloud without an rgb/rgba
 // field reads as 0).  *n = points in the file, *width / *height as in its header.  want_normals: the file must hold
-// normal_x / normal_y / normal_z / curvature, which go to nrm [cap][3] / curv [cap] (either may be NULL).
+// normal_x / normal_y / normal_z / curvature, which go to nrm [cap][3] / curv [cap] (either may be NULL).  want_labels:
+// the file must hold a label field, which goes to labels [cap] (may be NULL) as the 32 bits written.
 static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* nrm, float* curv, bool want_normals,
-                           size_t cap, size_t* n_out, int* width, int* height) {
+                           int* labels, bool want_labels, size_t cap, size_t* n_out, int* width, int* height) {
     if (!path) { r360_set_error("null path"); return -2; }
     std::ifstream f(path, std::ios::binary);
     if (!f) { r360_set_error("cannot open %s", path); return -1; }
@@ -420,6 +421,7 @@ static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* 
     if (N != W * H) { r360_set_error("%s: POINTS %ld != WIDTH*HEIGHT %ld", path, N, W * H); return -1; }
     int ix = -1, iy = -1, iz = -1, ic = -1;
     int in[4] = {-1, -1, -1, -1};   // normal_x, normal_y, normal_z, curvature
+    int il = -1;                    // label
     std::vector<size_t> foff(F.size());
     size_t rec = 0;
     for (size_t k = 0; k < F.size(); ++k) {
@@ -435,13 +437,16 @@ static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* 
         else if (p.name == "rgba" || p.name == "rgb") ic = (int)k;
         else if (p.name == "normal_x") in[0] = (int)k; else if (p.name == "normal_y") in[1] = (int)k;
         else if (p.name == "normal_z") in[2] = (int)k; else if (p.name == "curvature") in[3] = (int)k;
+        else if (p.name == "label") il = (int)k;
     }
     if (ix < 0 || iy < 0 || iz < 0) { r360_set_error("%s: no x/y/z fields", path); return -1; }
     if (want_normals && (in[0] < 0 || in[1] < 0 || in[2] < 0 || in[3] < 0)) {
         r360_set_error("%s: no normal_x/normal_y/normal_z/curvature fields", path);
         return -1;
     }
+    if (want_labels && il < 0) { r360_set_error("%s: no label field", path); return -1; }
     const bool normals = want_normals && (nrm || curv);
+    const bool lab = want_labels && labels;
     const size_t n = (size_t)N;
     if (n_out) *n_out = n;
     if (width) *width = (int)W;
@@ -481,6 +486,9 @@ static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* 
                 const std::string& s = toks[t];
                 for (int q = 0; q < 4; ++q)
                     if (normals && (int)k == in[q]) w[q] = (s == "nan" || s == "NaN") ? NAN : strtof(s.c_str(), nullptr);
+                if (lab && (int)k == il && i < m)   // 4294967295 and -1 are the same 32 bits
+                    labels[i] = (int)(uint32_t)(F[k].type == 'I' ? (unsigned long long)strtoll(s.c_str(), nullptr, 10)
+                                                                 : strtoull(s.c_str(), nullptr, 10));
                 if ((int)k == ix || (int)k == iy || (int)k == iz)
                     v[(int)k == ix ? 0 : (int)k == iy ? 1 : 2] = (s == "nan" || s == "NaN") ? NAN : strtod(s.c_str(), nullptr);
                 else if ((int)k == ic) {
@@ -524,6 +532,10 @@ static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* 
                 }
                 store_normal(i, w);
             }
+            if (lab) {
+                if (F[il].size == 4 && F[il].type != 'F') memcpy(&labels[i], at(i, il), 4);   // the bits
+                else labels[i] = (int)(long long)field_value(at(i, il), F[il]);
+            }
         }
     } else {
         r360_set_error("%s: unknown DATA %s", path, data.c_str());
@@ -534,12 +546,82 @@ static int pcd_read_fields(const char* path, float* xyz, uint32_t* rgba, float* 
 
 extern "C" int r360_pcd_read(const char* path, float* xyz, uint32_t* rgba, size_t cap, size_t* n_out, int* width,
                              int* height) {
-    return pcd_read_fields(path, xyz, rgba, nullptr, nullptr, false, cap, n_out, width, height);
+    return pcd_read_fields(path, xyz, rgba, nullptr, nullptr, false, nullptr, false, cap, n_out, width, height);
 }
 
 extern "C" int r360_pcd_read_normals(const char* path, float* xyz, uint32_t* rgba, float* normals, float* curvature,
                                      size_t cap, size_t* n) {
-    return pcd_read_fields(path, xyz, rgba, normals, curvature, true, cap, n, nullptr, nullptr);
+    return pcd_read_fields(path, xyz, rgba, normals, curvature, true, nullptr, false, cap, n, nullptr, nullptr);
+}
+
+extern "C" int r360_pcd_read_labels(const char* path, float* xyz, uint32_t* rgba, int* labels, size_t cap, size_t* n) {
+    return pcd_read_fields(path, xyz, rgba, nullptr, nullptr, false, labels, true, cap, n, nullptr, nullptr);
+}
+
+// pcl::PointXYZRGBL: x y z rgba label, 20 bytes per point, unorganised; label is unsigned, so -1 is written as 4294967295.
+// The modes and the codec are r360_pcd_write's.
+extern "C" int r360_pcd_write_labels(const char* path, const float* xyz, const uint32_t* rgba, const int* labels, size_t n,
+                                     int mode) {
+    // binary_compressed records the block's size in 32 bits
+    if (!path || (n && !xyz) || mode < 0 || mode > 2 || n > (size_t)1 << 30 || (mode == 2 && n >= (size_t)1 << 27)) {
+        r360_set_error("bad argument");
+        return -2;
+    }
+    std::ofstream o(path, std::ios::binary);
+    if (!o) { r360_set_error("cannot create %s", path); return -1; }
+    o << "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgba label\nSIZE 4 4 4 4 4\n"
+         "TYPE F F F U U\nCOUNT 1 1 1 1 1\nWIDTH " << n << "\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS " << n << "\n";
+    // one point's five 4-byte fields
+    auto fields = [&](size_t i, uint32_t* w) {
+        memcpy(w, &xyz[3 * i], 12);
+        w[3] = rgba ? rgba[i] : 0u;
+        w[4] = labels ? (uint32_t)labels[i] : 0u;
+    };
+    if (mode == 0) {
+        o << "DATA ascii\n";
+        std::string line;
+        char buf[32];
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t w[5];
+            fields(i, w);
+            line.clear();
+            for (int k = 0; k < 5; ++k) {
+                if (k >= 3) {
+                    snprintf(buf, sizeof buf, "%u", w[k]);
+                } else {
+                    float v;
+                    memcpy(&v, &w[k], 4);
+                    if (std::isnan(v)) snprintf(buf, sizeof buf, "nan");
+                    else snprintf(buf, sizeof buf, "%.8g", (double)v);
+                }
+                line += buf;
+                line += k == 4 ? '\n' : ' ';
+            }
+            o.write(line.data(), (std::streamsize)line.size());
+        }
+    } else {
+        std::vector<uint8_t> rec(20 * n);
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t w[5];
+            fields(i, w);
+            if (mode == 1) memcpy(&rec[20 * i], w, 20);
+            else for (int k = 0; k < 5; ++k) memcpy(&rec[4 * (k * n + i)], &w[k], 4);   // field-major
+        }
+        if (mode == 1) {
+            o << "DATA binary\n";
+            o.write((const char*)rec.data(), (std::streamsize)rec.size());
+        } else {
+            o << "DATA binary_compressed\n";
+            const std::vector<uint8_t> z = lzf_compress(rec.data(), rec.size());
+            const uint32_t zs = (uint32_t)z.size(), us = (uint32_t)rec.size();
+            o.write((const char*)&zs, 4);
+            o.write((const char*)&us, 4);
+            o.write((const char*)z.data(), (std::streamsize)z.size());
+        }
+    }
+    o.close();
+    if (!o) { r360_set_error("write failed: %s", path); return -1; }
+    return 0;
 }
 
 // pcl::PointXYZRGBNormal: x y z rgba normal_x normal_y normal_z curvature, 32 bytes per point, unorganised.  The modes

@@ -420,6 +420,61 @@ int launch_normals(hipStream_t st, const uint4* pts, const float4* spts, size_t 
                    const unsigned long long* keys, size_t table_cap, const unsigned* start, const unsigned* cnt, double lim2,
                    int k, const float* view, int n_view, float4* out, NormalHdr* hdr, const NormalEval& ev);
 
+// ------------------------------------------------------------------ Euclidean clusters (kernels/cluster_kernels.hip, host/clusters.cpp)
+constexpr unsigned R360_CLUSTER_CHUNK = 4096;      // members per workgroup of the moment sums
+// counts and error bits that cross to the host: 1 a find walk overran n steps, 2 a union overran n retries, 4 the list of
+// kept components overflowed, 8 a member list position out of range
+struct ClusterHdr { unsigned long long n_components, n_kept, n_clustered, n_zero; unsigned err, pad; };
+struct ClusterRec { int root, size; };             // a component within the size bounds
+struct ClusterBounds { unsigned mn[3], mx[3]; };   // floats as order-preserving unsigned
+// the parity hook's output beside ClusterState::root, NULL in the product calls
+struct ClusterEval { int* comp_size; };
+// What the cluster extraction holds on the device, grown on demand and freed with the context; the grid is ctx->outl's.
+struct ClusterState {
+    DevBuf<ClusterHdr> d_hdr; PinnedBuf<ClusterHdr> h_hdr;
+    DevBuf<float> nrm_in;                // [n][3] a host cloud's normals
+    DevBuf<int> parent, root, csize;     // [n] the forest, every row's root (-1 dropped), members per root
+    DevBuf<int> crank;                   // [n] a kept root's rank
+    DevBuf<int> comp_size;               // [n] the parity hook
+    DevBuf<unsigned> keep, kpos;         // [n] root of a kept component, and the flags' exclusive prefix
+    DevBuf<unsigned> mflag, mpos;        // [n] label >= 0, and the flags' exclusive prefix
+    DevBuf<ClusterRec> list;             // kept components in root order
+    PinnedBuf<ClusterRec> h_list;
+    PinnedBuf<unsigned> h_tab;           // staging of the three tables below
+    DevBuf<int> rank_root;               // [n_clusters] roots in rank order
+    DevBuf<unsigned> off, cpre;          // [n_clusters + 1] first member / first chunk of every cluster
+    DevBuf<int> key[2], val[2];          // [n_clustered] (label, input index) pairs of the stable split passes
+    DevBuf<double> partial, mean;        // [chunks][6] workgroup sums, [n_clusters][3] centroids
+    DevBuf<ClusterBounds> bounds;        // [n_clusters]
+    DevBuf<int> labels;                  // [n] the running call's labels at the input index
+    DevBuf<r360_cluster_info> info;      // [n_clusters] the running call's records
+    size_t n_info = 0;
+    DevBuf<int> map_labels;              // [map_n] the map's labels in the map's order, while map_valid
+    DevBuf<r360_cluster_info> map_info;
+    size_t map_n = 0, map_n_info = 0;
+    bool map_valid = false;              // cleared by whatever changes the map
+};
+int launch_clu_init(hipStream_t st, size_t n, int* parent, int* csize, int* root, int* labels, const ClusterEval& ev);
+// nrm: NULL (plain form) or the normals, nstride floats apart; thr: the dot product's threshold
+int launch_clu_union(hipStream_t st, const float4* spts, size_t nf, const OutlierGrid& G, const unsigned long long* keys,
+                     size_t table_cap, const unsigned* start, const unsigned* cnt, double lim2, const float* nrm,
+                     int nstride, double thr, int* parent, size_t n, ClusterHdr* hdr);
+int launch_clu_flatten(hipStream_t st, size_t n, const unsigned* pslot, int* parent, int* root, int* csize, ClusterHdr* hdr);
+int launch_clu_mark(hipStream_t st, size_t n, const int* root, const int* csize, int min_size, int max_size, unsigned* keep,
+                    ClusterHdr* hdr, const ClusterEval& ev);
+int launch_clu_list(hipStream_t st, size_t n, const unsigned* keep, const unsigned* kpos, const int* csize, ClusterRec* list,
+                    size_t list_cap, ClusterHdr* hdr);
+int launch_clu_label(hipStream_t st, size_t n, size_t nk, const int* rank_root, int* crank, const int* root,
+                     const unsigned* keep, int* labels, unsigned* mflag);
+int launch_clu_members(hipStream_t st, size_t n, const unsigned* mflag, const unsigned* mpos, const int* labels, int* key,
+                       int* val, size_t m, ClusterHdr* hdr);
+int launch_clu_bitflag(hipStream_t st, size_t m, const int* key, int bit, unsigned* flag);
+int launch_clu_split(hipStream_t st, size_t m, const int* key, const int* val, const unsigned* flag, const unsigned* fpos,
+                     const ClusterHdr* hdr, int* key_out, int* val_out);
+int launch_clu_moments(hipStream_t st, const uint4* pts, const int* val, size_t nk, size_t n_chunks, const int* rank_root,
+                       const unsigned* off, const unsigned* cpre, double* partial, double* mean, ClusterBounds* bounds,
+                       r360_cluster_info* info);
+
 // ------------------------------------------------------------------ Generalized-ICP (kernels/gicp_kernels.hip, host/gicp.cpp)
 // GicpGrid, the uniform grid over a cloud's bounding box, and the host-only logic: host/gicp_host.h
 constexpr int R360_GICP_KMAX = 32;      // k_correspondences the kNN kernel's LDS lists hold
@@ -585,6 +640,7 @@ struct r360_ctx {
     GicpState gicp;                        // Generalized-ICP clouds, indices and pass buffers (host/gicp.cpp)
     OutlierState outl;                     // outlier filters: sparse grid, scores, compaction (host/outliers.cpp)
     NormalState nrm;                       // surface normals: a call's output, the map's normals (host/normals.cpp)
+    ClusterState clu;                      // Euclidean clusters: forest, member lists, records, the map's labels (host/clusters.cpp)
     TopoState topo;                        // spectral partitioning: matrices, cluster lists, scratch (host/topo.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
