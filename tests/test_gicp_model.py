@@ -136,6 +136,121 @@ def test_host_logic_check_runs(root, tmp_path):
     assert p.returncode == 0 and "gicp host check ok" in p.stdout, p.stderr + p.stdout
 
 
+def _host_check_exe(root, tmp_path):
+    exe = tmp_path / "gicp_host_check"
+    p = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", f"{root}/tools/gicp_host_check.cpp",
+                        "-o", str(exe)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return exe
+
+
+def test_crafted_clouds_get_the_grids_they_claim(root, tmp_path):
+    """Every crafted cloud of _gicp_cases.CLOUDS through the library's own gicp_build_grid (tools/gicp_host_check.cpp
+    with file arguments, which also checks the invariant ring_bound2 rests on): the shape is the table's and the numpy
+    port's, to the bit of h."""
+    exe = _host_check_exe(root, tmp_path)
+    names = list(GC.CLOUDS)
+    files = []
+    for name in names:
+        files.append(str(tmp_path / f"{name}.f32"))
+        GC.cloud(name).tofile(files[-1])
+    p = subprocess.run([str(exe)] + files, capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stderr + p.stdout
+    lines = [ln.split() for ln in p.stdout.splitlines() if ln.startswith("grid ")]
+    assert len(lines) == len(names), p.stdout
+    for name, ln in zip(names, lines):
+        dim, h = tuple(int(v) for v in ln[1:4]), np.float32(float(ln[4]))
+        pdim, ph, _, _ = GC.choose_grid(GC.cloud(name))
+        print(name, GC.cloud(name).shape[0], dim, h)
+        assert dim == pdim and h == ph, (name, dim, pdim, h, ph)
+        want = GC.CLOUDS[name][1]
+        assert want is None or dim == want, (name, dim, want)
+    grid = {name: GC.choose_grid(GC.cloud(name)) for name in names}
+    # what each cloud is there for
+    assert GC.cloud("room512").shape[0] == GC.DIRECT and GC.cloud("room513").shape[0] == GC.DIRECT + 1
+    assert (GC.cloud("sheet")[:, 2] == 0.5).all() and grid["sheet"][0][2] == 1
+    for name in ("rod", "rod1024", "ribbon"):   # the capped axis: h at the bisection's lower bound, to float rounding
+        c = GC.cloud(name)
+        emax = float((c.max(axis=0) - c.min(axis=0)).max())
+        assert abs(float(grid[name][1]) * (GC.MAXDIM - 1) / emax - 1.0) <= 2.0 ** -22, name
+    assert {grid["rod"][0][0], grid["rod1024"][0][0]} == {GC.MAXDIM - 1, GC.MAXDIM}
+    # two clusters a kilometre apart: the cell columns between them are empty
+    c, (dim, _, inv, mn) = GC.cloud("two_clusters"), grid["two_clusters"]
+    used = np.unique(np.clip(np.floor((c[:, 0] - mn[0]) * inv), 0, dim[0] - 1))
+    assert dim[0] - used.size >= 490, (dim, used)
+    order = np.argsort(c[:, 0], kind="stable")
+    assert not np.array_equal(order, np.arange(c.shape[0]))   # shuffled: index order is not spatial order
+
+
+@pytest.mark.parametrize("name", list(GC.CLOUDS))
+def test_crafted_clouds_are_decided(name):
+    m = GC.model_cloud(name)
+    n = m.xyz.shape[0]
+    old, kd, cd = GC.knn_decided(m), GC.knn_decided_ties(m), GC.cov_decided_ties(m)
+    print(f"{name}: n={n} undecided kNN {(~old).sum()} by the gap alone, {(~kd).sum()} with ties, covariances {(~cd).sum()}")
+    assert (old <= kd).all()   # the extended rule only adds
+    if name in GC.TIED:
+        assert kd.all() and (~old).sum() > 50   # the ties are there, and the extended rule decides every one
+    else:
+        assert (~kd).sum() <= GC.MAX_UNDECIDED * n and (~cd).sum() <= GC.MAX_UNDECIDED * n
+    if name == "dups":
+        assert cd.all()
+        c = GC.cloud(name)
+        assert c.shape[0] == 700 and np.unique(c, axis=0).shape[0] == 600   # 100 rows are exact copies
+    if name.startswith("lattice"):
+        assert GC.exact_cloud(GC.cloud(name)) and np.abs(GC.cloud(name)).max() < 2.0
+    if name == "lattice_plane":
+        assert cd.all()
+        assert np.abs(m.C - np.diag([1.0, 1.0, GC.make_params().gicp_epsilon])).max() == 0.0
+
+
+def test_eval_poses_leave_the_targets_box():
+    """The four poses of the eval stage put hundreds of source points beyond five of the six faces of the target's
+    box (where the query's cell is clamped), and the cases that compare sums have no undecided correspondence."""
+    ms, mt = GC.model_pair(*GC.EVAL_PAIR)
+    dim, h, _, _ = GC.choose_grid(mt.xyz)
+    assert min(GC.GATES) < float(h) < GC.GATES[0]   # one gate below the target's cell edge, one above
+    reached = np.zeros(6, int)
+    counts = []
+    for name, X in GC.eval_poses().items():
+        out = GC.outside_faces(ms.xyz, mt.xyz, X)
+        assert out.max() > 100, (name, out)
+        reached = np.maximum(reached, out)
+        for gate in GC.GATES:
+            p = GC.make_params(gate=gate)
+            _, _, _, _, n, d2, second = GM.eval_at(ms, mt, X, p)
+            und = int((~GC.corr_decided(d2, second, p.max_corr_dist)).sum())
+            print(f"{name} gate {gate}: outside {out.tolist()} n_corr {n} undecided {und}")
+            counts.append(n)
+            assert und <= GC.MAX_UNDECIDED * ms.xyz.shape[0]
+            assert und == 0 or name in GC.EVAL_CORR_ONLY, (name, gate, und)
+    assert (reached > 100).sum() == 5, reached
+    assert min(counts) < 10 and max(counts) == ms.xyz.shape[0]
+
+
+def test_gate_lattice_ties_at_exactly_the_gate():
+    s, t = GC.gate_lattice()
+    assert GC.exact_cloud(s) and GC.exact_cloud(t) and s.shape[0] == 648
+    p = GC.make_params(gate=0.125)
+    ms, mt = GM.Cloud(s, p), GM.Cloud(t, p)
+    corr, _, _, _, n, d2, second = GM.eval_at(ms, mt, np.eye(4), p)
+    assert n == 0 and (corr == -1).all() and (d2 == 2.0 ** -6).all()   # the gate is strict
+    assert (second == d2).sum() == 576                                 # 8 of the 9 x columns tie two ways
+    above = GC.make_params(gate=float(np.nextafter(np.float32(0.125), np.float32(1.0))))
+    corr, _, _, _, n, _, _ = GM.eval_at(ms, mt, np.eye(4), above)
+    assert n == 648 and np.array_equal(corr, GC.gate_lattice_expected())
+
+
+@pytest.mark.parametrize("k", GC.K_ENDS)
+def test_k_ends_are_decided(k):
+    for c in GC.model_pair_with(*GC.K_PAIR, k=k) + tuple(GC.model_room(n, 31, k) for n in (k, 600, 2000)):
+        n = c.xyz.shape[0]
+        assert c.knn.shape == (n, k)
+        assert (~GC.knn_decided(c)).sum() <= GC.MAX_UNDECIDED * n and (~GC.cov_decided(c)).sum() <= GC.MAX_UNDECIDED * n
+    assert GC.choose_grid(GC.room(k, 31))[0] == (1, 1, 1) and GC.choose_grid(GC.room(600, 31))[0] != (1, 1, 1)
+    assert GC.WRAP_PAIR[0] > GC.PASS_WRAP
+
+
 def test_gicp_dropin_compiles(root):
     """tests/dropin/gicp_dropin.cpp: RegisterPairRGBD360's Generalized-ICP call sequence through compat.h, g++ alone."""
     p = subprocess.run(["g++", "-std=c++17", "-O0", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", f"-I{root}/include",

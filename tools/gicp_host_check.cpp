@@ -1,5 +1,7 @@
 // Stand-alone check of Generalized-ICP's host-only logic (rgbd360_amd/csrc/host/gicp_host.h): intake, the grid's
-// sizing and counting sort, the 6x6 solve and the inner loop's accept / stop rule fed with a canned quadratic.
+// sizing and counting sort (with the invariant the kernels' ring bound rests on, on thin, capped and mostly empty
+// grids), the 6x6 solve and the inner loop's accept / stop rule fed with a canned quadratic.  With file arguments
+// (float32 x y z rows) it checks and prints each file's grid instead.
 // Meant for the host sanitizers, no GPU and no HIP:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/gicp_host_check.cpp -o gicp_host_check
 #include "../rgbd360_amd/csrc/host/gicp_host.h"
@@ -38,7 +40,81 @@ static void check_grid(const std::vector<float>& xyz) {
     }
 }
 
-int main() {
+// What ring_bound2 (kernels/gicp_kernels.hip) assumes of a built grid: the offsets are monotone and end at n, every
+// dim is in 1 .. R360_GICP_MAXDIM, and every point lies within 1 % of a cell edge of the box of the cell it was sorted
+// into, on every axis, the clamped last cell included.  Returns the grid.
+static GicpGrid check_ring_invariant(const std::vector<float>& xyz) {
+    std::vector<float> pts, sorted;
+    std::vector<unsigned> start;
+    gicp_intake(xyz.data(), xyz.size() / 3, pts);
+    const size_t n = pts.size() / 4;
+    GicpGrid G;
+    gicp_build_grid(pts, G, sorted, start);
+    const size_t cells = (size_t)G.dim[0] * G.dim[1] * G.dim[2];
+    EXPECT(start.size() == cells + 1 && start[0] == 0 && start[cells] == n);
+    for (int a = 0; a < 3; ++a) EXPECT(G.dim[a] >= 1 && G.dim[a] <= R360_GICP_MAXDIM);
+    const double h = (double)G.h, slack = 0.01 * h;
+    for (size_t c = 0; c < cells; ++c) {
+        EXPECT(start[c] <= start[c + 1]);
+        const size_t cc[3] = {c % (size_t)G.dim[0], (c / (size_t)G.dim[0]) % (size_t)G.dim[1],
+                              c / ((size_t)G.dim[0] * (size_t)G.dim[1])};
+        for (unsigned q = start[c]; q < start[c + 1]; ++q)
+            for (int a = 0; a < 3; ++a) {
+                const double x = (double)sorted[4 * q + a], lo = (double)G.mn[a] + (double)cc[a] * h;
+                EXPECT(x >= lo - slack && x <= lo + h + slack);
+            }
+    }
+    return G;
+}
+
+// the crafted clouds of tests/_gicp_cases.py, by recipe (the generator differs, the shapes do not)
+static void check_crafted_grids() {
+    std::mt19937 rng(11);
+    std::uniform_real_distribution<float> u01(0.f, 1.f);
+    std::normal_distribution<float> gauss(0.f, 1.f);
+    for (int rep = 0; rep < 8; ++rep) {   // the capped axis falls to 1023 or 1024 cells with the rounding: several draws
+        std::vector<float> sheet(3 * 900), rod(3 * 2000), ribbon(3 * 7000), two(3 * 2000);
+        for (size_t i = 0; i < 900; ++i) { sheet[3 * i] = 3.f * u01(rng); sheet[3 * i + 1] = 2.f * u01(rng); sheet[3 * i + 2] = 0.5f; }
+        for (size_t i = 0; i < 2000; ++i) {
+            rod[3 * i] = 10.f * u01(rng); rod[3 * i + 1] = 0.004f * u01(rng); rod[3 * i + 2] = 0.0002f * gauss(rng);
+            const float off = i % 2 ? 1000.f : 0.f;   // interleaved: index order is not spatial order
+            two[3 * i] = off + 6.f * u01(rng) - 3.f; two[3 * i + 1] = 4.f * u01(rng) - 2.f; two[3 * i + 2] = 3.f * u01(rng) - 1.5f;
+        }
+        for (size_t i = 0; i < 7000; ++i) {
+            ribbon[3 * i] = 10.f * u01(rng); ribbon[3 * i + 1] = 0.05f * u01(rng); ribbon[3 * i + 2] = 0.0005f * gauss(rng);
+        }
+        GicpGrid G = check_ring_invariant(sheet);
+        EXPECT(G.dim[0] >= 36 && G.dim[0] <= 38 && G.dim[1] >= 24 && G.dim[1] <= 26 && G.dim[2] == 1);
+        G = check_ring_invariant(rod);
+        EXPECT((G.dim[0] == 1023 || G.dim[0] == 1024) && G.dim[1] == 1 && G.dim[2] == 1);
+        G = check_ring_invariant(ribbon);
+        EXPECT((G.dim[0] == 1023 || G.dim[0] == 1024) && G.dim[1] >= 5 && G.dim[1] <= 6 && G.dim[2] == 1);
+        G = check_ring_invariant(two);
+        EXPECT(G.dim[0] >= 499 && G.dim[0] <= 503 && G.dim[1] == 2 && G.dim[2] == 2);
+        check_grid(sheet); check_grid(rod); check_grid(ribbon); check_grid(two);
+    }
+}
+
+// gicp_host_check FILE...: each file holds float32 x y z rows; prints "grid dx dy dz h" for it after the same checks
+static int grids_of_files(int argc, char** argv) {
+    for (int k = 1; k < argc; ++k) {
+        std::FILE* f = std::fopen(argv[k], "rb");
+        EXPECT(f);
+        std::vector<float> xyz;
+        float buf[3];
+        while (std::fread(buf, sizeof(float), 3, f) == 3) xyz.insert(xyz.end(), buf, buf + 3);
+        std::fclose(f);
+        EXPECT(!xyz.empty());
+        const GicpGrid G = check_ring_invariant(xyz);
+        check_grid(xyz);
+        std::printf("grid %d %d %d %.9g\n", G.dim[0], G.dim[1], G.dim[2], (double)G.h);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) return grids_of_files(argc, argv);
+    check_crafted_grids();
     std::mt19937 rng(7);
     std::uniform_real_distribution<float> u(-1.f, 1.f);
     const float nan = std::numeric_limits<float>::quiet_NaN(), inf = std::numeric_limits<float>::infinity();
