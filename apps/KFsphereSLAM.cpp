@@ -41,9 +41,18 @@
 // the normals of --map-normals, which it then requires and follows.  It prints one more line, "map clusters: <points>
 // points, <components> components, <clusters> kept, largest <size>".  --save-clusters file.pcd writes the labelled map
 // (binary, x y z rgba label).
+// --map-planes DIST,MIN[,MAX] peels the final map's RANSAC planes where it lies (r360::GlobalMap360::segmentPlanes:
+// pcl::SACSegmentation's plane search with distance threshold DIST m, planes of at least MIN points, at most MAX of
+// them, 8 by default), after --clean-map and --map-normals; with --map-normals an inlier's normal must also agree with
+// the plane's.  It prints one more line, "map planes: <points> points, <planes> planes, <in planes> points in planes,
+// largest <size>".  --save-planes file.pcd writes the map labelled by plane (binary, x y z rgba label).  --remove-planes
+// then drops the plane points (r360::GlobalMap360::removePlanes) before --map-clusters, which so reports the objects
+// rather than the room; the removal invalidates the normals, so it is refused together with an angle in --map-clusters,
+// and --save-map then writes what is left without normals.
 //   usage: KFsphereSLAM --synthetic-frames a,b,c,... [occlusion] [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]
 //                       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]
 //                       [--map-normals K,R] [--save-map file.pcd] [--map-clusters TOL,MIN[,ANGLE_DEG]] [--save-clusters file.pcd]
+//                       [--map-planes DIST,MIN[,MAX]] [--save-planes file.pcd] [--remove-planes]
 //                       (--clean-map also takes cluster:TOL,MIN)
 //          KFsphereSLAM --synthetic <n_frames> [occlusion] ...
 //          KFsphereSLAM <dir with sphere_images_<n>.bin> <first> <step> [occlusion] ...
@@ -100,6 +109,10 @@ int main(int argc, char** argv) {
     r360_cluster_params cluster_prm;
     r360_cluster_default_params(&cluster_prm);
     std::string save_clusters;                           // --save-clusters
+    bool map_planes = false, remove_planes = false;      // --map-planes, --remove-planes
+    r360_sac_params plane_prm;
+    r360_sac_default_params(&plane_prm);
+    std::string save_planes;                             // --save-planes
     for (int k = 1; k < argc; ++k) {
         const std::string a = argv[k];
         if (a == "--clean-map" && k + 1 < argc) {
@@ -153,6 +166,14 @@ int main(int argc, char** argv) {
                 cluster_prm.eps_angle = deg * 3.14159265359f / 180.f;
             }
         }
+        else if (a == "--save-planes" && k + 1 < argc) save_planes = argv[++k];
+        else if (a == "--remove-planes") remove_planes = true;
+        else if (a == "--map-planes" && k + 1 < argc) {
+            map_planes = true;
+            const int got = std::sscanf(argv[++k], "%f,%d,%d", &plane_prm.distance_threshold, &plane_prm.min_inliers,
+                                        &plane_prm.max_planes);
+            bad_arg = bad_arg || got < 2;
+        }
         else if (a == "--submaps") submaps = true;
         else if (a == "--synthetic-frames" && k + 1 < argc) { frames_arg = argv[++k]; synthetic = true; }
         else if (a == "--synthetic" && k + 1 < argc) { n_synth = std::atoi(argv[++k]); synthetic = true; }
@@ -167,11 +188,13 @@ int main(int argc, char** argv) {
     }
     for (int k = 0; k < n_synth && frames_arg.empty(); ++k) order.push_back(k);
     bad_arg = bad_arg || (cluster_normals && !map_normals) || (!save_clusters.empty() && !map_clusters);
+    bad_arg = bad_arg || ((remove_planes || !save_planes.empty()) && !map_planes) || (remove_planes && cluster_normals);
     if (bad_arg || (synthetic && order.empty()) || (!synthetic && pos.size() < 3)) {
         std::fprintf(stderr, "usage: %s --synthetic-frames a,b,c,... [occlusion] | --synthetic <n> [occlusion] | <dir> <first> <step> "
                              "[occlusion]   [--min-gap G] [--kf-dist D] [--save graph.g2o] [--submaps]\n"
                              "       [--robust huber:D | cauchy:D] [--reject-chi2 T] [--false-loop I,J] [--clean-map sor:K,MUL[,D] | radius:R,N]\n"
                              "       [--map-normals K,R] [--save-map file.pcd] [--map-clusters TOL,MIN[,ANGLE_DEG]] [--save-clusters file.pcd]\n"
+                             "       [--map-planes DIST,MIN[,MAX]] [--save-planes file.pcd] [--remove-planes]\n"
                              "  --robust       loop edges get the kernel, of width D on sqrt(chi2); chain and PbMap edges stay quadratic\n"
                              "  --reject-chi2  after each optimisation loop edges with chi2 > T are deactivated and the graph is optimised again\n"
                              "  --false-loop   when keyframe J is added, also add a wrong loop edge I -> J (demonstration)\n"
@@ -186,7 +209,12 @@ int main(int argc, char** argv) {
                              "  --clean-map cluster:TOL,MIN  keeps the connected components of 'closer than TOL m' with at least MIN points\n"
                              "  --map-clusters the final map's Euclidean clusters (tolerance in m, least size), after --clean-map; with an angle\n"
                              "                 in degrees two neighbours' normals must also agree within it (needs --map-normals)\n"
-                             "  --save-clusters  the clustered map as a binary PCD file with a label field (needs --map-clusters)\n", argv[0]);
+                             "  --save-clusters  the clustered map as a binary PCD file with a label field (needs --map-clusters)\n"
+                             "  --map-planes   the final map's RANSAC planes (distance threshold in m, least size, at most MAX planes, 8 by\n"
+                             "                 default), after --clean-map and --map-normals; with --map-normals an inlier's normal must agree\n"
+                             "  --save-planes  the map labelled by plane as a binary PCD file with a label field (needs --map-planes)\n"
+                             "  --remove-planes  drops the plane points before --map-clusters (needs --map-planes; not with an angle in\n"
+                             "                 --map-clusters: the removal invalidates the normals)\n", argv[0]);
         return 1;
     }
     const bool edge_report = robust_kind != R360_GRAPH_KERNEL_NONE || reject_chi2 >= 0.0 || false_from >= 0;
@@ -473,6 +501,18 @@ int main(int argc, char** argv) {
             std::printf("map normals: %zu points, %zu short, %.3f neighbours on average\n", st.n_in, st.n_short,
                         st.n_finite ? double(st.sum_neighbors) / double(st.n_finite) : 0.0);
         }
+        if (map_planes) {
+            r360_sac_stats st;
+            map.segmentPlanes(plane_prm, map_normals, &st);
+            std::vector<r360_sac_plane> planes;
+            map.getPlanes(planes);
+            int largest = 0;
+            for (const r360_sac_plane& p : planes) largest = std::max(largest, p.size);
+            std::printf("map planes: %zu points, %zu planes, %zu points in planes, largest %d\n", st.n_in, st.n_planes,
+                        st.n_in_planes, largest);
+            if (!save_planes.empty()) map.savePCDPlaneLabels(save_planes, 1);
+            if (remove_planes) map.removePlanes(plane_prm, map_normals);
+        }
         if (map_clusters) {
             r360_cluster_stats st;
             map.cluster(cluster_prm, cluster_normals, &st);
@@ -483,7 +523,7 @@ int main(int argc, char** argv) {
             if (!save_clusters.empty()) map.savePCDLabels(save_clusters, 1);
         }
         if (!save_map.empty()) {
-            if (map_normals) {
+            if (map_normals && !remove_planes) {
                 map.savePCDNormals(save_map, 1);
             } else {
                 r360::PointCloud cloud;

@@ -41,9 +41,15 @@ using r360::GraphOptimizer;
 using r360::NormalEstimation;
 using r360::PbMap;
 using r360::Plane;
+using r360::ModelCoefficients;
 using r360::PointIndices;
 using r360::RegisterPhotoICP;
 using r360::RegisterRGBD360;
+using r360::SACSegmentation;
+using r360::SACMODEL_PLANE;
+using r360::SACMODEL_PARALLEL_PLANE;
+using r360::SACMODEL_PERPENDICULAR_PLANE;
+using r360::SAC_RANSAC;
 // Map360.h / TopologicalMap360.h / Relocalizer360.h: opt-in, since call-site files written before these classes
 // existed declare a reduced Map360 of their own
 #ifdef RGBD360_COMPAT_MAP360

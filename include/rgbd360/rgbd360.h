@@ -239,6 +239,16 @@ struct PointIndices {
     std::vector<int> indices;
 };
 
+// A model's coefficients (pcl::ModelCoefficients): a plane's a, b, c, d with a x + b y + c z + d = 0 and |abc| = 1.
+struct ModelCoefficients {
+    std::vector<float> values;
+};
+
+// pcl::SacModel / the sample-consensus methods SACSegmentation takes: the three plane models and RANSAC.  The other
+// enumerators of PCL have no counterpart; SACSegmentation throws on any other number.
+enum SacModel { SACMODEL_PLANE = 0, SACMODEL_PARALLEL_PLANE = 15, SACMODEL_PERPENDICULAR_PLANE = 9 };
+enum { SAC_RANSAC = 0 };
+
 class Context {
   public:
     explicit Context(int device = 0) { check(r360_ctx_create(device, &h_), "r360_ctx_create"); }
@@ -955,6 +965,42 @@ class GlobalMap360 {
         check(r360_pcd_write_labels(path.c_str(), cloud.xyz.data(), cloud.rgba.data(), labels.data(), cloud.size(), mode),
               "GlobalMap360::savePCDLabels");
     }
+    // RANSAC planes of the map where it lies (r360_ctx_map_sac_planes): plane labels and records stay on the GPU, valid
+    // until the map next changes.  use_normals: the normals gate on the map's normals (estimateNormals first)
+    void segmentPlanes(const r360_sac_params& params, bool use_normals = false, r360_sac_stats* stats = nullptr) {
+        check(r360_ctx_map_sac_planes(ctx_->get(), &params, use_normals ? 1 : 0, stats), "GlobalMap360::segmentPlanes");
+    }
+    // the map's plane labels in the order of download() (-1: in no plane); throws when the map changed since segmentPlanes
+    void getPlaneLabels(std::vector<int>& labels) const {
+        size_t n = 0;
+        check(r360_ctx_map_download_plane_labels(ctx_->get(), nullptr, 0, &n), "GlobalMap360::getPlaneLabels");
+        labels.resize(n);
+        check(r360_ctx_map_download_plane_labels(ctx_->get(), labels.data(), n, &n), "GlobalMap360::getPlaneLabels");
+    }
+    // the planes' records, in extraction order
+    void getPlanes(std::vector<r360_sac_plane>& planes) const {
+        size_t n = 0;
+        check(r360_ctx_map_plane_info(ctx_->get(), nullptr, 0, &n), "GlobalMap360::getPlanes");
+        planes.resize(n);
+        check(r360_ctx_map_plane_info(ctx_->get(), planes.data(), n, &n), "GlobalMap360::getPlanes");
+    }
+    // segments, then drops the plane points / keeps only them (r360_ctx_map_filter_planes), in HBM; the map's normals,
+    // cluster labels and plane labels become invalid
+    void removePlanes(const r360_sac_params& params, bool use_normals = false, r360_sac_stats* stats = nullptr) {
+        check(r360_ctx_map_filter_planes(ctx_->get(), &params, use_normals ? 1 : 0, 0, stats), "GlobalMap360::removePlanes");
+    }
+    void keepPlanes(const r360_sac_params& params, bool use_normals = false, r360_sac_stats* stats = nullptr) {
+        check(r360_ctx_map_filter_planes(ctx_->get(), &params, use_normals ? 1 : 0, 1, stats), "GlobalMap360::keepPlanes");
+    }
+    // the map with its plane labels as a PointXYZRGBL file (r360_pcd_write_labels; mode as r360_pcd_write)
+    void savePCDPlaneLabels(const std::string& path, int mode = 0) const {
+        PointCloud cloud;
+        std::vector<int> labels;
+        download(cloud);
+        getPlaneLabels(labels);
+        check(r360_pcd_write_labels(path.c_str(), cloud.xyz.data(), cloud.rgba.data(), labels.data(), cloud.size(), mode),
+              "GlobalMap360::savePCDPlaneLabels");
+    }
   private:
     std::shared_ptr<Context> keep_;
     Context* ctx_;
@@ -1052,6 +1098,83 @@ class EuclideanClusterExtraction {
     r360_cluster_stats stats_ = {0, 0, 0, 0, 0};
     std::vector<int> labels_;
     std::vector<r360_cluster_info> info_;
+};
+
+// pcl::SACSegmentation with PCL's names for the three plane models and RANSAC, on the GPU of the calling thread's
+// default context or of the Context given (r360_cloud_sac_planes with max_planes = 1).  segment()
+// returns the one largest plane: its inliers ascending and a, b, c, d; both are empty when no plane has
+// getMinInliers() points (3 by default; PCL reports an empty model when RANSAC finds none).  Extensions:
+// setInputNormals / setNormalAngle select the normals gate (where PCL has SACSegmentationFromNormals), setSeed the
+// counter-based sampler's seed, setMinInliers the smallest plane reported.  The input cloud and normals are
+// referenced, not copied: they must outlive segment().
+class SACSegmentation {
+  public:
+    SACSegmentation() { init(); }
+    explicit SACSegmentation(Context& ctx) : ctx_(&ctx) { init(); }
+    void setModelType(int model) {
+        if (model == SACMODEL_PLANE) prm_.constraint = R360_SAC_NONE;
+        else if (model == SACMODEL_PERPENDICULAR_PLANE) prm_.constraint = R360_SAC_PERPENDICULAR;
+        else if (model == SACMODEL_PARALLEL_PLANE) prm_.constraint = R360_SAC_PARALLEL;
+        else throw std::invalid_argument("SACSegmentation::setModelType: only the three plane models exist here");
+        model_ = model;
+    }
+    int getModelType() const { return model_; }
+    void setMethodType(int method) {
+        if (method != SAC_RANSAC) throw std::invalid_argument("SACSegmentation::setMethodType: only SAC_RANSAC exists here");
+    }
+    int getMethodType() const { return SAC_RANSAC; }
+    void setDistanceThreshold(double threshold) { prm_.distance_threshold = float(threshold); }
+    double getDistanceThreshold() const { return prm_.distance_threshold; }
+    void setMaxIterations(int n) { prm_.max_iterations = n; }
+    int getMaxIterations() const { return prm_.max_iterations; }
+    void setProbability(double probability) { prm_.probability = float(probability); }
+    double getProbability() const { return prm_.probability; }
+    void setOptimizeCoefficients(bool optimize) { prm_.optimize = optimize ? 1 : 0; }
+    bool getOptimizeCoefficients() const { return prm_.optimize != 0; }
+    void setAxis(float x, float y, float z) { prm_.axis[0] = x; prm_.axis[1] = y; prm_.axis[2] = z; }
+    void setEpsAngle(double radians) { prm_.eps_angle = float(radians); }
+    double getEpsAngle() const { return prm_.eps_angle; }
+    void setInputCloud(const PointCloud& cloud) { cloud_ = &cloud; }
+    void setInputNormals(const PointCloudNormal& normals) { normals_ = &normals; }   // extension
+    void setNormalAngle(double radians) { prm_.normal_angle = float(radians); }      // extension
+    void setSeed(unsigned long long seed) { prm_.seed = seed; }                      // extension
+    void setMinInliers(int n) { prm_.min_inliers = n; }                              // extension
+    int getMinInliers() const { return prm_.min_inliers; }
+    const r360_sac_stats& stats() const { return stats_; }
+    const r360_sac_plane& getPlaneInfo() const { return plane_; }
+    void segment(PointIndices& inliers, ModelCoefficients& coefficients) {
+        if (!cloud_) throw std::invalid_argument("SACSegmentation::segment: no input cloud");
+        if (normals_ && normals_->size() != cloud_->size())
+            throw std::invalid_argument("SACSegmentation::segment: normals and cloud differ in size");
+        Context& c = ctx_ ? *ctx_ : default_context();
+        const size_t n = cloud_->size();
+        std::vector<int> labels(n, -1);
+        size_t np = 0;
+        check(r360_cloud_sac_planes(c.get(), cloud_->xyz.data(), normals_ ? normals_->normals.data() : nullptr, n, &prm_,
+                                    labels.data(), &plane_, 1, &np, &stats_),
+              "SACSegmentation::segment");
+        inliers.indices.clear();
+        coefficients.values.clear();
+        if (np == 0) return;
+        inliers.indices.reserve(size_t(plane_.size));
+        for (size_t i = 0; i < n; ++i)
+            if (labels[i] == 0) inliers.indices.push_back(int(i));
+        for (int k = 0; k < 4; ++k) coefficients.values.push_back(float(plane_.coef[k]));
+    }
+  private:
+    void init() {
+        r360_sac_default_params(&prm_);
+        prm_.max_planes = 1;
+        prm_.min_inliers = 3;
+        std::memset(&plane_, 0, sizeof plane_);
+    }
+    Context* ctx_ = nullptr;
+    const PointCloud* cloud_ = nullptr;
+    const PointCloudNormal* normals_ = nullptr;
+    int model_ = SACMODEL_PLANE;
+    r360_sac_params prm_;
+    r360_sac_stats stats_ = {0, 0, 0, 0, 0};
+    r360_sac_plane plane_;
 };
 
 // ------------------------------------------------------------------ Generalized-ICP

@@ -845,9 +845,9 @@ int r360_pcd_read_normals(const char* path, float* xyz, uint32_t* rgba, float* n
  * r360_cloud_clusters_eval (parity hook): root [n] the smallest input index of the row's component (-1 dropped),
  * comp_size [n] the component's size before the size bounds (-1 dropped).
  * r360_ctx_map_cluster: labels and records of the context's map, kept on the device in the map's order until the map
- * next changes (r360_ctx_map_reset, _add_cloud, _add_frame, _filter_outliers, _filter_clusters).  use_normals without
- * valid map normals is an error (< 0); an empty map gives 0 and zero stats; an error leaves the map, its normals and its
- * labels as they were.
+ * next changes (r360_ctx_map_reset, _add_cloud, _add_frame, _filter_outliers, _filter_clusters, _filter_planes).
+ * use_normals without valid map normals is an error (< 0); an empty map gives 0 and zero stats; an error leaves the map,
+ * its normals and its labels as they were.
  * r360_ctx_map_download_labels / r360_ctx_map_cluster_info: an error (< 0) when the map has no valid labels; *n is the
  * map's size / the number of clusters either way; cap < *n is an error (< 0); a NULL array: only *n.
  * r360_ctx_map_filter_clusters: clusters, then keeps exactly the map points with label >= 0, compacted in HBM: the map
@@ -874,6 +874,76 @@ int r360_ctx_map_filter_clusters(r360_ctx* ctx, const r360_cluster_params* param
                                  r360_cluster_stats* stats);
 int r360_pcd_write_labels(const char* path, const float* xyz, const uint32_t* rgba, const int* labels, size_t n, int mode);
 int r360_pcd_read_labels(const char* path, float* xyz, uint32_t* rgba, int* labels, size_t cap, size_t* n);
+
+/* ---------------------------------------------------------------- RANSAC plane segmentation
+ * pcl::SACSegmentation with SACMODEL_PLANE / _PERPENDICULAR_PLANE / _PARALLEL_PLANE and SAC_RANSAC, and the loop of
+ * PCL's cluster-extraction recipe that peels planes until a fraction is left, restated (PCL is not pinned) for a host
+ * cloud and for the context's global map where it lies.  The statement is tests/sac_model.py and DESIGN.md §5b-5.
+ * Everything is double of the float inputs, left to right, uncontracted.
+ * A row with a non-finite coordinate is dropped: label -1, never sampled, never an inlier; n_finite counts the others.
+ * Plane of three points: u = p1 - p0, v = p2 - p0, n = u x v, s = (nx^2 + ny^2) + nz^2; degenerate (scored 0) iff s is
+ * not a finite number > 0; otherwise n /= sqrt(s), d = -((nx p0x + ny p0y) + nz p0z).
+ * A point is an inlier iff |((a x + b y) + c z) + d| <= (double)distance_threshold (closed) and, when normals ([n][3])
+ * are given, |(nx a + ny b) + nz c| >= cos((double)normal_angle); a row whose normal has a non-finite component is
+ * never an inlier but stays in the pool.
+ * Constraint on hypotheses, with â the axis normalised in double: PERPENDICULAR |n.â| >= cos(eps_angle) (the plane's
+ * normal within eps_angle of the axis), PARALLEL |n.â| <= sin(eps_angle) (the plane parallel to the axis); a
+ * hypothesis that fails scores 0.  The refined plane is not re-checked.
+ * Sampling is counter-based: mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z>>27) * 0x94D049BB133111EB; z ^ z>>31.  Draw j of hypothesis h of plane p over a pool of m:
+ * (mix(mix(mix(mix(seed) ^ p) ^ h) ^ j) * m) >> 64.  a = draw(0, m), b = draw(1, m-1), c = draw(2, m-2); if b >= a: b++;
+ * with lo < hi the two so far: if c >= lo: c++; if c >= hi: c++.  Positions index the pool: the remaining rows in
+ * ascending input index.
+ * Search for one plane over a pool of m: hypotheses are scored in rounds of R360_SAC_ROUND; after each round best is
+ * the highest count so far (ties to the lowest h), w = best / m, q = 1 - w w w clipped to [DBL_EPSILON, 1 - DBL_EPSILON],
+ * k = log(1 - probability) / log(q); the search goes on while evaluated < max_iterations and (double)evaluated < k.
+ * optimize: when the best hypothesis has >= 3 inliers, the plane through their centroid whose normal is the
+ * eigenvector of the smallest eigenvalue of their covariance (fp64, two passes, / size) replaces it and the inliers are
+ * selected again from the pool.
+ * Peel: for p = 0, 1, ... stop when p = max_planes, the pool is smaller than max(3, min_inliers),
+ * (double)pool <= (double)stop_fraction * n_finite, or the plane found has fewer than min_inliers final inliers (it is
+ * not recorded, its points stay unlabelled); otherwise the final inliers get label p and leave the pool.
+ * r360_sac_plane: coef oriented so that the largest-magnitude component of the normal is positive (ties to the lower
+ * axis; all four numbers negated together), size the final inliers, raw_size the best hypothesis' count,
+ * best_hypothesis, evaluated, and centroid, eig (ascending) and curvature of the final inliers as in r360_cluster_info.
+ * r360_cloud_sac_planes: normals NULL selects the plain form.  labels [n], planes [planes_cap], n_planes and stats may
+ * be NULL; planes_cap < the number of planes is an error (< 0) that still sets *n_planes (and labels and stats).
+ * r360_cloud_sac_eval (parity hook, plane 0 over the whole finite cloud): with coef_in [n_hyp][4] the coefficients are
+ * scored as given; without, hypotheses 0 .. n_hyp - 1 are drawn, and samples [n_hyp][3] gets their input indices (-1
+ * with fewer than 3 finite rows).  coef [n_hyp][4] gets what was scored, NaN when degenerate or refused; count
+ * [n_hyp].  n_hyp <= 65536; the outputs may be NULL.
+ * r360_ctx_map_sac_planes: plane labels and records of the context's map, kept on the device in the map's order until
+ * the map next changes.  use_normals without valid map normals is an error (< 0); an empty map gives 0 and zero stats;
+ * an error leaves the map, its normals and its labels as they were.  The cluster labels are not touched.
+ * r360_ctx_map_download_plane_labels / r360_ctx_map_plane_info: as r360_ctx_map_download_labels / _cluster_info.
+ * r360_ctx_map_filter_planes: segments, then drops the plane points (keep_planes 0) or keeps only them (1), compacted
+ * in HBM: order and bits are kept.  The map's normals, cluster labels and plane labels become invalid.
+ * Arguments: distance_threshold positive and finite, max_iterations 1 .. 65536, probability in (0, 1), max_planes
+ * 1 .. 64, min_inliers >= 3, stop_fraction in [0, 1), constraint one of the three, a constrained call's axis finite and
+ * non-zero, eps_angle and normal_angle in [0, pi/2], n <= 2^30 (R360_EINVAL otherwise, before any GPU work). */
+#define R360_SAC_ROUND 128
+#define R360_SAC_NONE 0
+#define R360_SAC_PERPENDICULAR 1
+#define R360_SAC_PARALLEL 2
+typedef struct {
+    float distance_threshold; int max_iterations; float probability; int optimize; int constraint; float axis[3];
+    float eps_angle, normal_angle; int max_planes, min_inliers; float stop_fraction; int reserved;
+    unsigned long long seed;
+} r360_sac_params;
+typedef struct {
+    double coef[4], centroid[3], eig[3], curvature; int size, raw_size, best_hypothesis, evaluated;
+} r360_sac_plane;
+typedef struct { size_t n_in, n_finite, n_planes, n_in_planes, n_evaluated; } r360_sac_stats;
+void r360_sac_default_params(r360_sac_params* params);
+int r360_cloud_sac_planes(r360_ctx* ctx, const float* xyz, const float* normals, size_t n, const r360_sac_params* params,
+                          int* labels, r360_sac_plane* planes, size_t planes_cap, size_t* n_planes, r360_sac_stats* stats);
+int r360_cloud_sac_eval(r360_ctx* ctx, const float* xyz, const float* normals, size_t n, const r360_sac_params* params,
+                        const double* coef_in, size_t n_hyp, int* samples, double* coef, int* count);
+int r360_ctx_map_sac_planes(r360_ctx* ctx, const r360_sac_params* params, int use_normals, r360_sac_stats* stats);
+int r360_ctx_map_download_plane_labels(r360_ctx* ctx, int* labels, size_t cap, size_t* n);
+int r360_ctx_map_plane_info(r360_ctx* ctx, r360_sac_plane* planes, size_t cap, size_t* n);
+int r360_ctx_map_filter_planes(r360_ctx* ctx, const r360_sac_params* params, int use_normals, int keep_planes,
+                               r360_sac_stats* stats);
 
 /* ---------------------------------------------------------------- Generalized-ICP
  * pcl::GeneralizedIterativeClosestPoint as Registration/RegisterPairRGBD360.cpp:109-149 calls it, restated (PCL is

@@ -183,6 +183,56 @@ CLUSTER_INFO_DTYPE = np.dtype([("size", np.int32), ("root", np.int32), ("min", n
                                ("curvature", np.float64)])
 assert CLUSTER_INFO_DTYPE.itemsize == C.sizeof(ClusterInfo)
 
+SAC_ROUND = 128           # R360_SAC_ROUND: hypotheses per round of the plane search
+SAC_NONE, SAC_PERPENDICULAR, SAC_PARALLEL = 0, 1, 2
+
+
+class SacParams(C.Structure):
+    """r360_sac_params — pcl::SACSegmentation's settings for the three plane models with SAC_RANSAC, and the peel loop's
+    (see include/rgbd360_hip.h); angles in radians."""
+    _fields_ = [("distance_threshold", C.c_float), ("max_iterations", C.c_int), ("probability", C.c_float),
+                ("optimize", C.c_int), ("constraint", C.c_int), ("axis", C.c_float * 3), ("eps_angle", C.c_float),
+                ("normal_angle", C.c_float), ("max_planes", C.c_int), ("min_inliers", C.c_int),
+                ("stop_fraction", C.c_float), ("reserved", C.c_int), ("seed", C.c_ulonglong)]
+
+    @classmethod
+    def default(cls) -> "SacParams":
+        p = cls()
+        lib().r360_sac_default_params(C.byref(p))
+        return p
+
+    @classmethod
+    def make(cls, **kw) -> "SacParams":
+        """The defaults with the given fields replaced (axis: three floats)."""
+        p = cls.default()
+        for k, v in kw.items():
+            if k == "axis":
+                p.axis[0], p.axis[1], p.axis[2] = (float(a) for a in v)
+            elif k in ("reserved",) or k not in dict(cls._fields_):
+                raise TypeError(f"SacParams has no field {k!r}")
+            else:
+                setattr(p, k, v)
+        return p
+
+
+class SacStats(C.Structure):
+    """r360_sac_stats — what one plane segmentation saw."""
+    _fields_ = [("n_in", C.c_size_t), ("n_finite", C.c_size_t), ("n_planes", C.c_size_t), ("n_in_planes", C.c_size_t),
+                ("n_evaluated", C.c_size_t)]
+
+
+class SacPlane(C.Structure):
+    """r360_sac_plane — one plane's record."""
+    _fields_ = [("coef", C.c_double * 4), ("centroid", C.c_double * 3), ("eig", C.c_double * 3), ("curvature", C.c_double),
+                ("size", C.c_int), ("raw_size", C.c_int), ("best_hypothesis", C.c_int), ("evaluated", C.c_int)]
+
+
+SAC_PLANE_DTYPE = np.dtype([("coef", np.float64, 4), ("centroid", np.float64, 3), ("eig", np.float64, 3),
+                            ("curvature", np.float64), ("size", np.int32), ("raw_size", np.int32),
+                            ("best_hypothesis", np.int32), ("evaluated", np.int32)])
+assert SAC_PLANE_DTYPE.itemsize == C.sizeof(SacPlane)
+SAC_MAX_PLANES = 64
+
 
 class GraphParams(C.Structure):
     """r360_graph_params — pose-graph optimisation settings (see include/rgbd360_hip.h)."""
@@ -553,6 +603,14 @@ _SIGS = [
     ("r360_ctx_map_download_labels", C.c_int, [_P, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r360_ctx_map_cluster_info", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r360_ctx_map_filter_clusters", C.c_int, [_P, C.POINTER(ClusterParams), C.c_int, C.POINTER(ClusterStats)]),
+    ("r360_sac_default_params", None, [C.POINTER(SacParams)]),
+    ("r360_cloud_sac_planes", C.c_int, [_P, _FP, _FP, C.c_size_t, C.POINTER(SacParams), _IP, _P, C.c_size_t,
+                                        C.POINTER(C.c_size_t), C.POINTER(SacStats)]),
+    ("r360_cloud_sac_eval", C.c_int, [_P, _FP, _FP, C.c_size_t, C.POINTER(SacParams), _DP, C.c_size_t, _IP, _DP, _IP]),
+    ("r360_ctx_map_sac_planes", C.c_int, [_P, C.POINTER(SacParams), C.c_int, C.POINTER(SacStats)]),
+    ("r360_ctx_map_download_plane_labels", C.c_int, [_P, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_ctx_map_plane_info", C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("r360_ctx_map_filter_planes", C.c_int, [_P, C.POINTER(SacParams), C.c_int, C.c_int, C.POINTER(SacStats)]),
     ("r360_pcd_write_labels", C.c_int, [C.c_char_p, _FP, _P, _IP, C.c_size_t, C.c_int]),
     ("r360_pcd_read_labels", C.c_int, [C.c_char_p, _FP, _P, _IP, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("r360_gicp_default_params", None, [C.POINTER(GicpParams)]),
@@ -997,6 +1055,76 @@ class Context:
         p = prm if prm is not None else ClusterParams.default()
         st = ClusterStats()
         _check(lib().r360_ctx_map_filter_clusters(self.h, C.byref(p), int(use_normals), C.byref(st)), "map_filter_clusters")
+        return st
+
+    def sac_planes(self, xyz, prm: "SacParams | None" = None, normals=None):
+        """pcl::SACSegmentation's RANSAC plane search on this context's GPU, peeled plane after plane
+        (r360_cloud_sac_planes); with `normals` [n,3] an inlier's normal must also lie within normal_angle of the
+        plane's.  Returns (labels [n] i32, the plane's extraction order or -1; planes, a SAC_PLANE_DTYPE array;
+        SacStats)."""
+        xyz, _ = _cloud_arrays(xyz, None)
+        p = prm if prm is not None else SacParams.default()
+        n = xyz.shape[0]
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert nrm is None or nrm.shape[0] == n
+        labels, st, np_ = np.full(n, -1, np.int32), SacStats(), C.c_size_t()
+        info = np.zeros(SAC_MAX_PLANES, SAC_PLANE_DTYPE)
+        _check(lib().r360_cloud_sac_planes(self.h, _fptr(xyz), None if nrm is None else _fptr(nrm), n, C.byref(p),
+                                           labels.ctypes.data_as(_IP), _vptr(info), SAC_MAX_PLANES, C.byref(np_),
+                                           C.byref(st)), "sac_planes")
+        return labels, info[:np_.value].copy(), st
+
+    def sac_eval(self, xyz, prm: "SacParams | None" = None, normals=None, n_hyp: int = SAC_ROUND, coef_in=None):
+        """Parity hook (r360_cloud_sac_eval) of plane 0 over the whole finite cloud: (samples [n_hyp,3] i32, coef
+        [n_hyp,4] f64, count [n_hyp] i32).  With coef_in [n_hyp,4] those coefficients are scored as they are."""
+        xyz, _ = _cloud_arrays(xyz, None)
+        p = prm if prm is not None else SacParams.default()
+        n = xyz.shape[0]
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert nrm is None or nrm.shape[0] == n
+        cin = None
+        if coef_in is not None:
+            cin = np.ascontiguousarray(coef_in, np.float64).reshape(-1, 4)
+            n_hyp = cin.shape[0]
+        samples = np.full((n_hyp, 3), -1, np.int32)
+        coef, count = np.full((n_hyp, 4), np.nan), np.zeros(n_hyp, np.int32)
+        _check(lib().r360_cloud_sac_eval(self.h, _fptr(xyz), None if nrm is None else _fptr(nrm), n, C.byref(p),
+                                         None if cin is None else _dptr(cin), n_hyp, samples.ctypes.data_as(_IP),
+                                         _dptr(coef), count.ctypes.data_as(_IP)), "sac_eval")
+        return samples, coef, count
+
+    def map_sac_planes(self, prm: "SacParams | None" = None, use_normals: bool = False) -> "SacStats":
+        """The same on the context's global map where it lies; plane labels and records stay in HBM, valid until the
+        map changes.  use_normals: the gate on the map's normals (map_estimate_normals first)."""
+        p = prm if prm is not None else SacParams.default()
+        st = SacStats()
+        _check(lib().r360_ctx_map_sac_planes(self.h, C.byref(p), int(use_normals), C.byref(st)), "map_sac_planes")
+        return st
+
+    def map_plane_labels(self) -> np.ndarray:
+        """The map's plane labels [n] i32 in the map's order; raises when the map changed since map_sac_planes."""
+        n = C.c_size_t()
+        _check(lib().r360_ctx_map_download_plane_labels(self.h, None, 0, C.byref(n)), "map_plane_labels")
+        labels = np.full(n.value, -1, np.int32)
+        _check(lib().r360_ctx_map_download_plane_labels(self.h, labels.ctypes.data_as(_IP), n.value, C.byref(n)),
+               "map_plane_labels")
+        return labels
+
+    def map_planes(self) -> np.ndarray:
+        """The map's plane records (SAC_PLANE_DTYPE); raises when the map changed since map_sac_planes."""
+        n = C.c_size_t()
+        _check(lib().r360_ctx_map_plane_info(self.h, None, 0, C.byref(n)), "map_planes")
+        info = np.zeros(n.value, SAC_PLANE_DTYPE)
+        _check(lib().r360_ctx_map_plane_info(self.h, _vptr(info), n.value, C.byref(n)), "map_planes")
+        return info
+
+    def map_filter_planes(self, prm: "SacParams | None" = None, use_normals: bool = False,
+                          keep_planes: bool = False) -> "SacStats":
+        """Segments the map and drops the plane points (keep_planes: keeps only them), where the map lies in HBM."""
+        p = prm if prm is not None else SacParams.default()
+        st = SacStats()
+        _check(lib().r360_ctx_map_filter_planes(self.h, C.byref(p), int(use_normals), int(keep_planes), C.byref(st)),
+               "map_filter_planes")
         return st
 
     def _gicp_set(self, fn, xyz, params, what):

@@ -307,7 +307,6 @@ extern "C" int r360_ctx_map_filter_clusters(r360_ctx* ctx, const r360_cluster_pa
     if (stats) *stats = z;
     M.cur = other;
     M.map_n = z.n_clustered;
-    N.map_valid = false;
-    ctx->clu.map_valid = false;
+    ctx->map_changed();
     return 0;
 }

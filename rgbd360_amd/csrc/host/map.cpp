@@ -201,8 +201,7 @@ extern "C" int r360_cloud_filter_voxel(r360_ctx* ctx, const float* xyz, const ui
 extern "C" int r360_ctx_map_reset(r360_ctx* ctx) {
     CHECK_ARG(ctx, "null ctx");
     ctx->vmap.map_n = 0;
-    ctx->nrm.map_valid = false;
-    ctx->clu.map_valid = false;
+    ctx->map_changed();
     return 0;
 }
 
@@ -220,8 +219,7 @@ extern "C" int r360_ctx_map_add_cloud(r360_ctx* ctx, const float* xyz, const uin
     if (bind_device(ctx->device)) return -1;
     if (map_reserve(ctx, n)) return -1;
     if (upload_cloud(ctx, xyz, rgba, n, M.map[M.cur].get() + M.map_n)) return -1;
-    ctx->nrm.map_valid = false;
-    ctx->clu.map_valid = false;
+    ctx->map_changed();
     return map_commit(ctx, n, leaf);
 }
 
@@ -276,8 +274,7 @@ extern "C" int r360_ctx_map_add_frame(r360_ctx* ctx, r360_frame* f, const float 
     memcpy(T.m, pose, sizeof T.m);
     if (launch_map_pack_frame(ctx->stream, P.v.cloud, P.v.rgb, per, rig, T, x_min, x_max, box, M.map[M.cur].get() + M.map_n))
         return -1;
-    ctx->nrm.map_valid = false;
-    ctx->clu.map_valid = false;
+    ctx->map_changed();
     return map_commit(ctx, n, leaf);
 }
 

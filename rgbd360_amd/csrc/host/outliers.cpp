@@ -219,8 +219,7 @@ extern "C" int r360_ctx_map_filter_outliers(r360_ctx* ctx, const r360_outlier_pa
         return rc;
     M.cur = other;
     M.map_n = m;
-    ctx->nrm.map_valid = false;
-    ctx->clu.map_valid = false;
+    ctx->map_changed();
     return 0;
 }
 

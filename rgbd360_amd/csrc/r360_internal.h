@@ -475,6 +475,69 @@ int launch_clu_moments(hipStream_t st, const uint4* pts, const int* val, size_t 
                        const unsigned* off, const unsigned* cpre, double* partial, double* mean, ClusterBounds* bounds,
                        r360_cluster_info* info);
 
+// ------------------------------------------------------------------ RANSAC planes (kernels/sac_kernels.hip, host/sac.cpp, host/sac_sample.h)
+constexpr int R360_SAC_TPB = 256;                  // the count kernel's workgroup: its points per stride
+constexpr int R360_SAC_MAXB = 256;                 // and its workgroups at most: larger pools stride
+constexpr unsigned R360_SAC_CHUNK = 4096;          // inliers per workgroup of the moment sums
+constexpr int R360_SAC_MAX_PLANES = 64;
+// What crosses to the host: once per round the best hypothesis so far, once per plane the selected inliers.  err: 1 a
+// list position out of range
+struct SacHdr {
+    int best_count, best_h;          // the highest count so far (-1 before the first round), ties to the lowest h
+    double best_coef[4];             // its coefficients (NaN when it scored 0 as degenerate or refused)
+    double ref_coef[4];              // the refined plane
+    unsigned long long n_finite, n_sel;
+    unsigned err, pad;
+};
+struct SacSearch {                   // one plane's hypotheses: constant over its rounds
+    unsigned long long seed;
+    unsigned p, m;                   // the plane's number, the pool's size
+    int constraint;
+    double axis[3], cos_eps, sin_eps;
+};
+struct SacGate { const float* nrm; int nstride; double thr, cos_n; };   // nrm NULL: the plain form
+// What the plane search holds on the device, grown on demand and freed with the context.
+struct SacState {
+    DevBuf<SacHdr> d_hdr; PinnedBuf<SacHdr> h_hdr;
+    DevBuf<float> nrm_in;                // [n][3] a host cloud's normals
+    DevBuf<int> pool[2];                 // [n] the remaining rows in ascending input index, and the next plane's
+    DevBuf<int> inl;                     // [n] one plane's inliers, ascending
+    DevBuf<unsigned> flag, fpos;         // [n] a selection's flags and their exclusive prefix
+    DevBuf<double> coef;                 // [max(R360_SAC_ROUND, n_hyp)][4] the round's (the hook's) hypotheses
+    DevBuf<int> count;                   // [max(R360_SAC_ROUND, n_hyp)] their inlier counts
+    DevBuf<int> samples;                 // [n_hyp][3] the parity hook
+    DevBuf<double> partial, mean;        // [chunks][6] workgroup sums, [3] the centroid
+    DevBuf<int> labels;                  // [n] the running call's labels at the input index
+    DevBuf<r360_sac_plane> info;         // [R360_SAC_MAX_PLANES] the running call's records
+    size_t n_info = 0;
+    DevBuf<int> map_labels;              // [map_n] the map's plane labels in the map's order, while map_valid
+    DevBuf<r360_sac_plane> map_info;
+    size_t map_n = 0, map_n_info = 0;
+    bool map_valid = false;              // cleared by map_changed()
+};
+int launch_sac_finite(hipStream_t st, const uint4* pts, size_t n, unsigned* flag, int* labels);
+int launch_sac_pool0(hipStream_t st, size_t n, const unsigned* flag, const unsigned* fpos, int* pool);
+// hypotheses h0 .. h0 + nh of the search: coef [nh][4] (NaN when scored 0), samples NULL or [nh][3] input indices
+int launch_sac_hyp(hipStream_t st, const uint4* pts, const int* pool, const SacSearch& S, int h0, int nh, double* coef,
+                   int* samples);
+// count [nh] += the pool's inliers of coef [nh][4], nh <= R360_SAC_ROUND; the caller has zeroed count
+int launch_sac_count(hipStream_t st, const uint4* pts, const int* pool, size_t m, const SacGate& G, const double* coef, int nh,
+                     int* count);
+int launch_sac_best(hipStream_t st, const int* count, const double* coef, int h0, int nh, SacHdr* hdr);
+// flag [m] over the pool's positions: inlier of the plane coef[0 .. 4) (a device address)
+int launch_sac_select(hipStream_t st, const uint4* pts, const int* pool, size_t m, const SacGate& G, const double* coef,
+                      unsigned* flag);
+int launch_sac_split(hipStream_t st, const int* pool, size_t m, const unsigned* flag, const unsigned* fpos, int* inl,
+                     size_t inl_cap, SacHdr* hdr);
+// the flagged rows get label p, the others move to `next` in order
+int launch_sac_peel(hipStream_t st, const int* pool, size_t m, const unsigned* flag, const unsigned* fpos, int p, int* labels,
+                    int* next, size_t n, SacHdr* hdr);
+// mean and covariance of pts[inl[0 .. cnt)], cnt >= 1.  rec NULL: the refined plane into hdr->ref_coef (cnt >= 3).
+// Otherwise the record *rec of a plane with these inliers, its coefficients hdr->ref_coef (refined) or hdr->best_coef.
+int launch_sac_moments(hipStream_t st, const uint4* pts, const int* inl, size_t cnt, double* partial, double* mean,
+                       SacHdr* hdr, r360_sac_plane* rec, bool refined, int raw_size, int evaluated);
+int launch_sac_keepflag(hipStream_t st, const int* labels, size_t n, int keep_planes, unsigned* flag);
+
 // ------------------------------------------------------------------ Generalized-ICP (kernels/gicp_kernels.hip, host/gicp.cpp)
 // GicpGrid, the uniform grid over a cloud's bounding box, and the host-only logic: host/gicp_host.h
 constexpr int R360_GICP_KMAX = 32;      // k_correspondences the kNN kernel's LDS lists hold
@@ -641,6 +704,7 @@ struct r360_ctx {
     OutlierState outl;                     // outlier filters: sparse grid, scores, compaction (host/outliers.cpp)
     NormalState nrm;                       // surface normals: a call's output, the map's normals (host/normals.cpp)
     ClusterState clu;                      // Euclidean clusters: forest, member lists, records, the map's labels (host/clusters.cpp)
+    SacState sac;                          // RANSAC planes: pools, hypotheses, records, the map's plane labels (host/sac.cpp)
     TopoState topo;                        // spectral partitioning: matrices, cluster lists, scratch (host/topo.cpp)
     r360_plane_queue* plane_q = nullptr;   // frames built on this ctx run their plane stage on this queue (batched)
     int device = 0;
@@ -760,6 +824,13 @@ struct r360_ctx {
     // Register() in flight (r360_register_async)
     int reg_pending = 0, reg_good = 0;
     float reg_info[36];
+    // The map's points changed: whatever was derived from them (normals, cluster labels, plane labels) is stale.  Every
+    // call that adds to, resets or compacts the map ends with this; a new derived stage adds its flag here alone.
+    void map_changed() {
+        nrm.map_valid = false;
+        clu.map_valid = false;
+        sac.map_valid = false;
+    }
 };
 
 struct ClamsDev {
